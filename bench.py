@@ -6,8 +6,17 @@ of every group's decision to pinned host memory.  Default workload: BASELINE con
 (100M pods / 1M nodes / 10k node groups), sharded over the N GPUs (strong scaling: the
 snapshot is fixed, each GPU streams 1/N of it).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4|2|3|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4|2|3|5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+unit, ms_per_step, ...).  `--full` adds everything else the benchmark measures or checks, each
+in runs of its own after the timed steps: the parity check against the C oracle, per-kernel
+and roofline figures, the resident RunOnce, host-side figures and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step computed (every group's totals and
+decision, the selections delivered with it; config 5: the orderings) as DIR/<name>.npy in
+float64, so that two builds can be compared output for output: the snapshot is generated
+from a fixed seed, the same from run to run.
 """
 from __future__ import annotations
 
@@ -176,6 +185,32 @@ def report(out: dict, parity_ok: bool) -> int:
         log("bench: PARITY MISMATCH against the C oracle: %s" % out.get("parity"))
         return PARITY_EXIT
     return 0
+
+
+DUMP_BUDGET = 64 << 20          # bytes --dump-outputs writes at most, over all its arrays
+
+
+def dump_arrays(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as path/<name>.npy, flat float64.  An array over its equal
+    share of DUMP_BUDGET is cut to a fixed sample of its elements (seeded: the same positions
+    in every run, in order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // 8 // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a).astype(np.float64).ravel()
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0xE5CA1A7E).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def decision_arrays(tot, dec, sel=None) -> dict:
+    """What a caller of the decision receives (esc_results, esc_selections), by name."""
+    out = {"totals_" + n: tot[n] for n in tot.dtype.names}
+    out.update(("decision_" + n, dec[n]) for n in dec.dtype.names)
+    if sel is not None:
+        out.update(zip(("selection_which", "selection_offsets", "selection_nodes"), sel))
+    return out
 
 
 def stage_layout(world: int, shard_world: int, multi, backend: str) -> list[str]:
@@ -451,11 +486,44 @@ def bench_order(args):
             ms = float(e.item())
         return ms
 
-    warm_ms = timed(ctx.sort_nodes, args.steps)
+    if args.dump_outputs and world > 1:
+        raise SystemExit("bench: --dump-outputs with --config 5 writes one rank's orderings: run it with --gpus 1")
+    if args.full:
+        warm_ms = timed(ctx.sort_nodes, args.steps)
+    else:
+        for _ in range(args.warmup):
+            ctx.sort_nodes()
     order_ms = cold(ctx.sort_nodes, args.steps)
+    n_memb, R = ctx.order_info()
+    if args.dump_outputs:
+        orders = {w: [ctx.group_order(g, w) for g in range(G)] for w in (0, 1)}
+        dump_arrays(args.dump_outputs, {
+            "order_oldest_first": np.concatenate(orders[0]), "order_oldest_first_counts": [len(o) for o in orders[0]],
+            "order_newest_first": np.concatenate(orders[1]), "order_newest_first_counts": [len(o) for o in orders[1]]})
+        del orders
+    headline = {
+        "metric": "config5 node orderings: memberships ordered/sec per decision (taint/untaint selection)",
+        "unit": "memberships/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": order_ms,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "dtype": "int64 keys",
+        "data": "synthetic (esc_synth.cpp config 5: 10M nodes, 100 groups, unique ns creation times)",
+    }
+    if not args.full:
+        if dist is not None:
+            tot = torch.tensor([n_memb], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(tot)
+            n_memb = int(tot.item())
+            dist.destroy_process_group()
+        if rank != 0:
+            return 0
+        return report(dict(headline, value=n_memb / (order_ms * 1e-3)), True)
     index_ms = timed(ctx.build_age_index, max(3, args.steps // 4))
     ctx.sort_nodes()
-    n_memb, R = ctx.order_info()
     nodes = s.nodes()
     if world == 1:
         want = soa.order_all(nodes, s.groups)
@@ -505,18 +573,8 @@ def bench_order(args):
     else:
         idx_passes = -(-(R + gbits) // 8)
         index_bytes = N * 24 + n_memb * (12 + idx_passes * 32)
-    out = {
-        "metric": "config5 node orderings: memberships ordered/sec per decision (taint/untaint selection)",
-        "value": n_memb / (order_ms * 1e-3),
-        "unit": "memberships/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": order_ms,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "dtype": "int64 keys",
-        "data": "synthetic (esc_synth.cpp config 5: 10M nodes, 100 groups, unique ns creation times)",
+    out = dict(headline, value=n_memb / (order_ms * 1e-3))
+    out.update({
         "config": {"workload": "config5: 10M nodes oldest-first / newest-first orderings, 100 node groups",
                    "nodes": N, "node_groups": G, "memberships": n_memb, "parallelism": "shard%d" % world},
         "roofline": {"bound": "hbm", "kernel": "per-decision ordering (k_ord_split + k_ord_packed)",
@@ -539,7 +597,7 @@ def bench_order(args):
         "selection_merge_ms": sel_ms,
         "segments_nonempty": int(sum(1 for c in counts if c)),
         "parity": how if parity else "MISMATCH vs C oracle",
-    }
+    })
     if dist is not None:
         dist.destroy_process_group()
     return report(out, parity)
@@ -679,6 +737,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=4, choices=sorted(CONFIGS) + [5])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check parity against the C oracle and measure the per-kernel, "
+                         "roofline, RunOnce, host-side and CPU-baseline figures (the --no-* options drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-host", action="store_true", help="skip the host-side packer / upload figures")
@@ -756,11 +819,12 @@ def main():
     args.no_select = args.no_select or args.no_order
     if not args.no_select:                            # and the walks' first nodes go out with it
         ctx.set_selections(SEL_SLACK, SEL_CAP)
-    n_memb = ctx.order_info()[0]
-    if multi:
-        pod_b, node_b = ctx.stream_bytes()            # every device's shard
-    else:
-        pod_b, node_b = stream_bytes(ctx, s, shard_rank, shard_world)
+    if args.full:
+        n_memb = ctx.order_info()[0]
+        if multi:
+            pod_b, node_b = ctx.stream_bytes()        # every device's shard
+        else:
+            pod_b, node_b = stream_bytes(ctx, s, shard_rank, shard_world)
     log("rank %d: shard pods [%d,%d), %.1f MB x %d replicas, setup %.1fs" %
         (rank, lo, hi, shard_bytes / 1e6, replicas, time.time() - t0))
 
@@ -784,10 +848,6 @@ def main():
     ctx.use_graph(args.graph)
     rccl_ranks = rccl_ranks_field(ctx.comm_size, multi, world, backend)
     ctx.k1_calibrate(16)                          # K1 shares to this device's rates (untimed, once per load)
-    fe, ff = ctx.k1_flush_entries()
-    k1_partials = {"entries": fe, "whole_row_entries": ff, "bytes": fe * 512,
-                   "note": "512-B pod-slot column partials K1 writes and K3 reads per decision (compact flush: "
-                           "only the columns a workgroup's share touches, DESIGN.md §4)"}
 
     def barrier():
         if dist is not None:
@@ -812,6 +872,46 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs:                           # the last timed step's decision, as a caller receives it
+        if multi or world == 1:
+            arrays = decision_arrays(*ctx.results(), sel=None if args.no_select else ctx.selections())
+        else:
+            from escalator_amd.dist import gather_results
+            arrays = decision_arrays(*gather_results(ctx))      # collective: every rank
+        if rank == 0:
+            dump_arrays(args.dump_outputs, arrays)
+
+    headline = {
+        "metric": "pod+node records evaluated/sec per scale decision & % HBM peak, 1/2/4/8 GPUs",
+        "value": (P + N) * args.steps / elapsed,
+        "unit": "records/s",
+        "n_gpus": n_gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic (deterministic counter-hash generator, escalator_amd/csrc/esc_synth.cpp)",
+        "config": {"workload": cfg["name"], "pods": P, "nodes": N, "node_groups": G,
+                   "parallelism": ("single-process x%d" % n_gpus) if multi else "shard%d" % world,
+                   "replicas_rotated": replicas},
+    }
+    if not args.full:
+        if dist is not None:
+            dist.destroy_process_group()
+        if rank != 0:
+            return 0
+        if n_gpus != args.gpus or (rccl_ranks is not None and rccl_ranks != args.gpus):
+            raise SystemExit("bench: n_gpus %d / rccl_ranks %s != --gpus %d" % (n_gpus, rccl_ranks, args.gpus))
+        return report(headline, True)
+
+    fe, ff = ctx.k1_flush_entries()
+    k1_partials = {"entries": fe, "whole_row_entries": ff, "bytes": fe * 512,
+                   "note": "512-B pod-slot column partials K1 writes and K3 reads per decision (compact flush: "
+                           "only the columns a workgroup's share touches, DESIGN.md §4)"}
 
     # Per-kernel device time of K1 (the dominant kernel), HIP events on the context's stream
     # (a multi-device context: device 0's).
@@ -864,8 +964,6 @@ def main():
     # K1's algorithmic bytes per launch on device 0 (its share of the pods)
     algo = pod_b // (len(multi) if multi else 1)
     achieved = algo / (k1_ms * 1e-3) / 1e9
-    records = P + N
-    value = records * args.steps / elapsed
     # shards are near-equal: rank 0's bytes x N (pods, the node index, the orderings); a
     # multi-device context reports every device's bytes already
     decision_bytes = (pod_b + node_b + (0 if args.no_order else n_memb * 16)) * (1 if multi else world)
@@ -879,22 +977,8 @@ def main():
     bmd = {"pods": int(md[0]), "nodes": nmd, "orderings": 12 * int(md[1]), "total": int(md[0]) + nmd + 12 * int(md[1])}
     frac_md = bmd["total"] / (ms_per_step * 1e-3) / (HBM_PEAK_GBS * 1e9 * n_gpus)
     probe = ctx.hbm_probe() if n_gpus == 1 else None
-    out = {
-        "metric": "pod+node records evaluated/sec per scale decision & % HBM peak, 1/2/4/8 GPUs",
-        "value": value,
-        "unit": "records/s",
-        "n_gpus": n_gpus,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic (deterministic counter-hash generator, escalator_amd/csrc/esc_synth.cpp)",
-        "config": {"workload": cfg["name"], "pods": P, "nodes": N, "node_groups": G,
-                   "parallelism": ("single-process x%d" % n_gpus) if multi else "shard%d" % world,
-                   "replicas_rotated": replicas},
+    out = dict(headline)
+    out.update({
         "hbm_frac_decision": decision_bytes / (ms_per_step * 1e-3) / (HBM_PEAK_GBS * 1e9 * n_gpus),
         "roofline": {"bound": "hbm", "kernel": "k_pod_reduce", "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -937,7 +1021,7 @@ def main():
                     "order) written by K4 to pinned host memory inside the step (esc_set_selections)"},
         "run_once": run_once,
         "parity": parity,
-    }
+    })
     if not args.no_host and n_gpus == 1 and shard_world == 1:
         up_ms, up_bytes = upload_ms(s, torch.device("cuda", local))
         out["snapshot_load"] = {"esc_load_ms": load_ms, "h2d_ms": up_ms, "h2d_bytes": up_bytes,

@@ -54,22 +54,22 @@ suite() {
 
 bench() {
     echo "[gpu] $(date +%T) bench config 4"
-    timeout -k 10 500 python3 -u bench.py --steps $STEPS --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; return 1; }
+    timeout -k 10 500 python3 -u bench.py --full --steps $STEPS --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; return 1; }
     cut -c1-900 $OUT/bench.json
     echo "[gpu] $(date +%T) bench rank 0 of 8"
-    timeout -k 10 300 python3 -u bench.py --shard-of 8 --steps 50 --warmup 10 --no-cpu-baseline \
+    timeout -k 10 300 python3 -u bench.py --full --shard-of 8 --steps 50 --warmup 10 --no-cpu-baseline \
         > $OUT/bench_shard8.json 2> $OUT/bench_shard8.err || { tail $OUT/bench_shard8.err; return 1; }
     cut -c1-900 $OUT/bench_shard8.json
     echo "[gpu] $(date +%T) bench config 5"
-    timeout -k 10 400 python3 -u bench.py --config 5 --steps $STEPS --warmup 3 > $OUT/bench5.json 2> $OUT/bench5.err || { tail $OUT/bench5.err; return 1; }
+    timeout -k 10 400 python3 -u bench.py --full --config 5 --steps $STEPS --warmup 3 > $OUT/bench5.json 2> $OUT/bench5.err || { tail $OUT/bench5.err; return 1; }
     cat $OUT/bench5.json
 }
 
 nosel() {      # the bench without selections (esc_set_selections off): their cost in the step
     echo "[gpu] $(date +%T) bench without selections: config 4, rank 0 of 8"
-    timeout -k 10 400 python3 -u bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-host --no-select \
+    timeout -k 10 400 python3 -u bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-host --no-select \
         > $OUT/bench_nosel.json 2> $OUT/bench_nosel.err || { tail $OUT/bench_nosel.err; return 1; }
-    timeout -k 10 300 python3 -u bench.py --shard-of 8 --steps 50 --warmup 10 --no-cpu-baseline --no-host --no-select \
+    timeout -k 10 300 python3 -u bench.py --full --shard-of 8 --steps 50 --warmup 10 --no-cpu-baseline --no-host --no-select \
         > $OUT/bench_shard8_nosel.json 2> $OUT/bench_shard8_nosel.err || { tail $OUT/bench_shard8_nosel.err; return 1; }
     python3 -c "
 import json
@@ -83,7 +83,7 @@ ablate() {     # NAME:A,B,..  the tail's roles dropped (measurement library, ESC
     args=$(args_of $name) || return 1
     for a in ${list//,/ }; do
         echo "[gpu] $(date +%T) ablate $name $a"
-        ESC_LIB_PATH=$PWD/escalator_amd/libescalator_hip_measure.so ESC_K3_ABLATE=$a timeout -k 10 300 python3 -u bench.py \
+        ESC_LIB_PATH=$PWD/escalator_amd/libescalator_hip_measure.so ESC_K3_ABLATE=$a timeout -k 10 300 python3 -u bench.py --full \
             $args --no-cpu-baseline --no-host --no-parity > $OUT/abl_${name}_$a.json 2> $OUT/abl_${name}_$a.err \
             || { tail $OUT/abl_${name}_$a.err; return 1; }
         python3 -c "
@@ -95,18 +95,18 @@ print('  $name a=$a step %.4f ms' % d['ms_per_step'], {k: round(x * 1e3, 1) for 
 
 rehearse2() {
     echo "[gpu] $(date +%T) N = 2 rehearsal: two gloo ranks on device 0"
-    ESC_BENCH_BACKEND=gloo ESC_BENCH_DEVICE=0 timeout -k 10 600 python3 -u bench.py --gpus 2 --steps 10 --warmup 3 \
+    ESC_BENCH_BACKEND=gloo ESC_BENCH_DEVICE=0 timeout -k 10 600 python3 -u bench.py --full --gpus 2 --steps 10 --warmup 3 \
         --no-cpu-baseline > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err || { tail -30 $OUT/bench_n2_gloo.err; return 1; }
     cut -c1-900 $OUT/bench_n2_gloo.json
     echo "[gpu] $(date +%T) N = 2 rehearsal: one process, two shards on device 0 (peer exchange)"
-    ESC_BENCH_DEVICES=0,0 timeout -k 10 600 python3 -u bench.py --gpus 2 --single-process --steps 10 --warmup 3 \
+    ESC_BENCH_DEVICES=0,0 timeout -k 10 600 python3 -u bench.py --full --gpus 2 --single-process --steps 10 --warmup 3 \
         --no-cpu-baseline > $OUT/bench_n2_multi.json 2> $OUT/bench_n2_multi.err || { tail -30 $OUT/bench_n2_multi.err; return 1; }
     cut -c1-900 $OUT/bench_n2_multi.json
 }
 
 rehearse2c5() {
     echo "[gpu] $(date +%T) N = 2 rehearsal of config 5: two gloo ranks on device 0"
-    ESC_BENCH_BACKEND=gloo ESC_BENCH_DEVICE=0 timeout -k 10 600 python3 -u bench.py --config 5 --gpus 2 --steps 10 \
+    ESC_BENCH_BACKEND=gloo ESC_BENCH_DEVICE=0 timeout -k 10 600 python3 -u bench.py --full --config 5 --gpus 2 --steps 10 \
         --warmup 3 > $OUT/bench5_n2_gloo.json 2> $OUT/bench5_n2_gloo.err || { tail -30 $OUT/bench5_n2_gloo.err; return 1; }
     cut -c1-900 $OUT/bench5_n2_gloo.json
 }
@@ -115,16 +115,16 @@ prof() {       # name
     local name=$1 a
     a=$(args_of $name) || return 1
     echo "[gpu] $(date +%T) prof $name: bench"
-    timeout -k 10 500 python3 -u bench.py $a > $OUT/pbench_$name.json 2> $OUT/pbench_$name.err || { tail -20 $OUT/pbench_$name.err; return 1; }
+    timeout -k 10 500 python3 -u bench.py --full $a > $OUT/pbench_$name.json 2> $OUT/pbench_$name.err || { tail -20 $OUT/pbench_$name.err; return 1; }
     echo "[gpu] $(date +%T) prof $name: kernel trace"
     timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$name -o run \
-        -- python3 bench.py $a --no-cpu-baseline --no-host > $OUT/trace_$name.log 2>&1 || { tail -20 $OUT/trace_$name.log; return 1; }
+        -- python3 bench.py --full $a --no-cpu-baseline --no-host > $OUT/trace_$name.log 2>&1 || { tail -20 $OUT/trace_$name.log; return 1; }
     echo "[gpu] $(date +%T) prof $name: pmc FETCH_SIZE"
     timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "(^|[ :])k_" --output-format csv -d $OUT/fetch_$name -o run \
-        -- python3 bench.py $a --no-cpu-baseline --no-host > $OUT/fetch_$name.log 2>&1 || { tail -20 $OUT/fetch_$name.log; return 1; }
+        -- python3 bench.py --full $a --no-cpu-baseline --no-host > $OUT/fetch_$name.log 2>&1 || { tail -20 $OUT/fetch_$name.log; return 1; }
     echo "[gpu] $(date +%T) prof $name: pmc WRITE_SIZE"
     timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "(^|[ :])k_" --output-format csv -d $OUT/write_$name -o run \
-        -- python3 bench.py $a --no-cpu-baseline --no-host > $OUT/write_$name.log 2>&1 || { tail -20 $OUT/write_$name.log; return 1; }
+        -- python3 bench.py --full $a --no-cpu-baseline --no-host > $OUT/write_$name.log 2>&1 || { tail -20 $OUT/write_$name.log; return 1; }
     local tr st fe wr
     tr=$(find $OUT/trace_$name -name "run_kernel_trace.csv" | head -1)
     st=$(find $OUT/trace_$name -name "run_kernel_stats.csv" | head -1)
@@ -159,7 +159,7 @@ rt() {         # name: rocprofv3 --runtime-trace (HIP API + kernels + copies; no
     a=$(args_of $name) || return 1
     echo "[gpu] $(date +%T) runtime trace $name"
     timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/rt_$name -o run \
-        -- python3 bench.py $a --no-cpu-baseline --no-host > $OUT/rt_$name.log 2>&1 || { tail -20 $OUT/rt_$name.log; return 1; }
+        -- python3 bench.py --full $a --no-cpu-baseline --no-host > $OUT/rt_$name.log 2>&1 || { tail -20 $OUT/rt_$name.log; return 1; }
 }
 
 pmcsq() {      # name: one SQ counter pass (<= 8 SQ counters)
@@ -168,7 +168,7 @@ pmcsq() {      # name: one SQ counter pass (<= 8 SQ counters)
     echo "[gpu] $(date +%T) pmc SQ $name"
     timeout -s KILL 400 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU \
         SQ_INSTS_LDS SQ_INSTS_VMEM_RD --kernel-include-regex "(^|[ :])k_" --output-format csv -d $OUT/sq_$name -o run \
-        -- python3 bench.py $a --no-cpu-baseline --no-host > $OUT/sq_$name.log 2>&1 || { tail -20 $OUT/sq_$name.log; return 1; }
+        -- python3 bench.py --full $a --no-cpu-baseline --no-host > $OUT/sq_$name.log 2>&1 || { tail -20 $OUT/sq_$name.log; return 1; }
     find $OUT/sq_$name -name "run_counter_collection.csv" -exec cp {} $PROF/pmc_sq_$name.csv \;
 }
 
@@ -179,9 +179,9 @@ variants() {   # comma-separated names
             lib=$PWD/escalator_amd/libescalator_hip_$v.so
             [ "$v" = base ] && lib=$PWD/escalator_amd/libescalator_hip.so
             echo "[gpu] $(date +%T) variant $v (rep $rep)"
-            ESC_LIB_PATH=$lib timeout -k 10 300 python3 -u bench.py --shard-of 8 --steps 50 --warmup 10 --no-cpu-baseline \
+            ESC_LIB_PATH=$lib timeout -k 10 300 python3 -u bench.py --full --shard-of 8 --steps 50 --warmup 10 --no-cpu-baseline \
                 > $OUT/var_${v}_shard8_$rep.json 2> $OUT/var_${v}_shard8_$rep.err || { tail $OUT/var_${v}_shard8_$rep.err; return 1; }
-            ESC_LIB_PATH=$lib timeout -k 10 400 python3 -u bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-host \
+            ESC_LIB_PATH=$lib timeout -k 10 400 python3 -u bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-host \
                 --no-parity > $OUT/var_${v}_full_$rep.json 2> $OUT/var_${v}_full_$rep.err || { tail $OUT/var_${v}_full_$rep.err; return 1; }
             python3 -c "
 import json
@@ -200,7 +200,7 @@ variants5() {  # config 5 (age-index build, orderings) per library build
             lib=$PWD/escalator_amd/libescalator_hip_$v.so
             [ "$v" = base ] && lib=$PWD/escalator_amd/libescalator_hip.so
             echo "[gpu] $(date +%T) variant $v config 5 (rep $rep)"
-            ESC_LIB_PATH=$lib timeout -k 10 400 python3 -u bench.py --config 5 --steps $STEPS --warmup 3 --no-cpu-baseline \
+            ESC_LIB_PATH=$lib timeout -k 10 400 python3 -u bench.py --full --config 5 --steps $STEPS --warmup 3 --no-cpu-baseline \
                 > $OUT/var5_${v}_$rep.json 2> $OUT/var5_${v}_$rep.err || { tail $OUT/var5_${v}_$rep.err; return 1; }
             python3 -c "
 import json

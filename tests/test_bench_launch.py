@@ -59,6 +59,39 @@ def test_parity_mismatch_fails_the_run(capsys):
     assert "sys.exit(main())" in src
 
 
+def test_dump_arrays_float64_within_budget_and_repeatable(tmp_path):
+    """--dump-outputs: every array lands as <name>.npy in float64; one over its share of the
+    64 MB budget is cut to the same sample of its elements in every run, in order."""
+    import numpy as np
+    assert bench.DUMP_BUDGET == 64 << 20
+    share = bench.DUMP_BUDGET // 8 // 2
+    big = np.arange(share + 1000, dtype=np.int64)
+    arrays = {"small": np.array([3, -1, 1 << 40], np.int64), "big": big}
+    for d in ("a", "b"):
+        bench.dump_arrays(str(tmp_path / d), arrays)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy"]
+    assert all(x.dtype == np.float64 and x.ndim == 1 for x in a.values())
+    assert np.array_equal(a["small"], [3.0, -1.0, float(1 << 40)])
+    assert len(a["big"]) == share and sum(x.nbytes for x in a.values()) <= bench.DUMP_BUDGET
+    assert np.all(np.diff(a["big"]) > 0) and np.isin(a["big"], big).all()      # a sample, in order
+    assert all(np.array_equal(a[n], b[n]) for n in arrays)
+
+
+def test_decision_arrays_names_every_field():
+    import numpy as np
+    from escalator_amd.context import DECISION_DTYPE, TOTALS_DTYPE
+    tot, dec = np.zeros(3, TOTALS_DTYPE), np.zeros(3, DECISION_DTYPE)
+    dec["delta"] = [1, -2, 0]
+    out = bench.decision_arrays(tot, dec)
+    assert set(out) == {"totals_" + n for n in TOTALS_DTYPE.names} | {"decision_" + n for n in DECISION_DTYPE.names}
+    assert list(out["decision_delta"]) == [1, -2, 0]
+    sel = (np.array([0, -1, 1]), np.array([0, 2, 2, 3]), np.array([7, 8, 9]))
+    out = bench.decision_arrays(tot, dec, sel)
+    assert list(out["selection_offsets"]) == [0, 2, 2, 3] and list(out["selection_nodes"]) == [7, 8, 9]
+
+
 def test_stage_layout_names_every_event():
     """The timing-mode stages the bench line reports at each shape."""
     base = ["k_pod_reduce", "k_step_tail", "k_order_split"]
