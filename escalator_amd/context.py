@@ -192,10 +192,22 @@ class Context:
         """This rank's pod shard (global indices from pod_offset) and the whole node table
         (every rank holds it; its share of the node work is the pairs it owns)."""
         L.check(self.lib.esc_set_replicas(self.handle, replicas), "esc_set_replicas")
-        ps, k1 = pod_soa(pods)
-        ns, k2 = node_soa(nodes)
+        self.load_pods(pods, pod_offset)
+        self.load_nodes(nodes)
+
+    def load_pods(self, pods: dict, pod_offset: int = 0):
+        """esc_load_pods alone: (re)loads this rank's pod shard.  With the nodes resident (a pod
+        re-list) the age index is rebuilt and the context stays usable; the previous decision's
+        selections are invalid (selections(): ESC_E_STATE) until the next decision."""
+        ps, keep = pod_soa(pods)
         L.check(self.lib.esc_load_pods(self.handle, C.byref(ps), pod_offset), "esc_load_pods")
+        del keep
+
+    def load_nodes(self, nodes: dict):
+        """esc_load_nodes alone: (re)loads the whole node table (a node re-list; pods stay)."""
+        ns, keep = node_soa(nodes)
         L.check(self.lib.esc_load_nodes(self.handle, C.byref(ns), 0, len(nodes["flags"])), "esc_load_nodes")
+        del keep
 
     def load_synth(self, s: Synth, pod_offset: int = 0, replicas: int = 1):
         L.check(self.lib.esc_set_replicas(self.handle, replicas), "esc_set_replicas")

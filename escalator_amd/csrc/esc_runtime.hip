@@ -225,6 +225,10 @@ struct esc_ctx {
     int32_t sel_slack = -1, sel_group_cap = 0;
     uint32_t *h_sel = nullptr, *h_sel_dev = nullptr;
     int64_t sel_words = 0;
+    // the last decision enqueued was given a selection target (sel_out): esc_selections reads
+    // h_cdec[].sel / h_sel only then.  Cleared by everything that changes or drops the target
+    // (esc_set_selections, esc_set_order_in_step, release_sort) and when h_cdec is allocated.
+    bool sel_valid = false;
     bool want_metrics = false;                                // K4 also writes the gauges
     esc_group_metrics* d_metrics = nullptr;
     int64_t* bound_pwords = nullptr;                          // caller-bound exchange buffer
@@ -652,9 +656,14 @@ void release_sort(esc_ctx* c) {
     for (int i = 0; i < 2; ++i) { dfree(c->d_mkeys[i]); dfree(c->d_mvals[i]); }
     c->mcap = 0;
     c->age_built = false;
+    // the regions are gone: orderings, steps with the ordering inside and selections are
+    // refused (ESC_E_STATE) until build_age_index succeeds again
+    c->age_ok = false;
+    c->sel_valid = false;
     dfree(c->d_g_memb);
     dfree(c->d_ostat); dfree(c->d_ord);
     c->n_pchunks = 0;
+    c->n_psmall = 0;
     c->n_chunks = 0;
     c->n_gpad = 0;
     dfree(c->d_hist); dfree(c->d_tot);
@@ -1263,6 +1272,7 @@ int32_t ensure_work(esc_ctx* c) {
     HIP_TRY(dalloc(&c->d_cdec, (size_t)G));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_cdec), (size_t)G * sizeof(DecCompact)));
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_cdec_dev), c->h_cdec, 0));
+    c->sel_valid = false;                                // fresh records: no decision has written them
     if (G <= HTOT_MAX_GROUPS) {
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_tot), (size_t)G * sizeof(esc_group_totals)));
         HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_tot_dev), c->h_tot, 0));
@@ -1907,7 +1917,10 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     c->cur = 0;
     c->pods_loaded = true;
     c->stale &= ~STALE_PODS;                          // a failed pod event's half-writes are gone
-    return ESC_OK;
+    // release_sort dropped the age index (its buffers may be held by captured steps); with the
+    // nodes resident (a pod re-list) it is rebuilt here, as esc_load_nodes ends (not over a
+    // node table a failed event left half-written: that one waits for esc_load_nodes)
+    return c->nodes_loaded && !(c->stale & STALE_NODES) ? build_age_index(c) : ESC_OK;
 }
 
 int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi) {
@@ -2568,6 +2581,7 @@ int32_t esc_decide(esc_ctx* c) {
     HIP_TRY(launch_node_groups(group_dev(c), node_dev(c), own_list(c), c->nodes.rows, c->d_trk_acc, c->d_nwords,
                                NGDecide{c->d_pwords, c->d_dec, c->zero_copy ? c->h_cdec_dev : c->d_cdec, sel_out(c), ng_trace},
                                c->stream));
+    c->sel_valid = sel_out(c).out != nullptr;
     c->ng_pending = false;
     c->tot_dec = true;
     if (!c->zero_copy)
@@ -2591,14 +2605,16 @@ int32_t esc_run(esc_ctx* c) {
     (void)nrep;
     c->tot_dec = true;
     if (c->order_in_step) { c->order_src = 0; c->sorted = true; }
-    if (!c->use_graph || c->timing) return enqueue_step(c, r, true, true);
-    return replay_step(c, c->graphs, r, true);
+    rc = !c->use_graph || c->timing ? enqueue_step(c, r, true, true) : replay_step(c, c->graphs, r, true);
+    c->sel_valid = rc == ESC_OK && sel_out(c).out != nullptr;   // (a captured step holds the same target)
+    return rc;
 }
 
 int32_t esc_set_order_in_step(esc_ctx* c, int32_t enable) {
     if (c && c->multi) return esc::multi_each(c, esc_set_order_in_step, enable);
     if (!c) return ESC_E_INVAL;
     c->order_in_step = enable != 0;
+    c->sel_valid = false;                               // the next decision's target differs
     drop_graphs(c);
     return ESC_OK;
 }
@@ -2649,6 +2665,7 @@ int32_t esc_set_selections(esc_ctx* c, int32_t slack, int32_t group_cap) {
     HIP_TRY(hipStreamSynchronize(c->stream));          // queued decisions may still write the buffer
     drop_graphs(c);                                     // captured steps hold the old target
     release_selections(c);
+    c->sel_valid = false;                               // no decision has written the new buffer
     // every block of 64 groups has a slot for its groups' runs at their largest (header +
     // group_cap nodes; k_node_groups): no decision overflows it
     const int64_t words = (((int64_t)c->gi.G + 63) / 64) * 64 * ((int64_t)group_cap + 1);
@@ -2701,6 +2718,11 @@ int32_t esc_selections(esc_ctx* c, int32_t* which, int64_t* offsets, int64_t* id
     esc_ctx* c0 = c->multi ? esc::multi_sub(c, 0) : c;
     if (!c0 || !c0->has_device) return ESC_E_NODEV;
     if (c0->sel_slack < 0 || !c0->h_cdec) return ESC_E_STATE;
+    // only a decision that ran with a selection target (sel_out) wrote the records read below:
+    // none since esc_set_selections / a reload, or the ordering not in the step, is refused,
+    // not reported as "no group asks for a walk"
+    for (int i = 0; c->multi ? esc::multi_sub(c, i) != nullptr : i < 1; ++i)
+        if (!(c->multi ? esc::multi_sub(c, i) : c)->sel_valid) return ESC_E_STATE;
     if (int32_t rc = esc_sync(c); rc != ESC_OK && rc != ESC_E_ORDER) return rc;
     // the ordering the selections come from gave up: they are invalid, as its orderings
     bool failed = false;

@@ -354,7 +354,13 @@ int32_t esc_packer_view(esc_packer* pk, esc_pod_soa* pods, esc_node_soa* nodes);
  * esc_load_nodes: copies the full node table (lo = 0, hi = n_nodes: every rank holds it)
  *   and builds its pair-major index (one entry per (label pair, node), sorted by pair then
  *   node — DESIGN.md §3); the decision reduces the pieces of the pairs this rank owns, and
- *   the age index (K5) lists the memberships of their groups.                        */
+ *   the age index (K5) lists the memberships of their groups.
+ * Either may be called alone once both have been (a pod re-list with the nodes resident, a
+ *   node re-list with the pods resident): both drop the age index, and both end by rebuilding
+ *   it when the node table is resident, so the context is usable — orderings in the step and
+ *   selections included — after either.  While no valid index exists (a failed build) every
+ *   call that reads it returns ESC_E_STATE.  A reload invalidates the previous decision's
+ *   selections (esc_selections: ESC_E_STATE until the next decision).                */
 int32_t esc_load_pods(esc_ctx* ctx, const esc_pod_soa* pods, int64_t global_offset);
 int32_t esc_load_nodes(esc_ctx* ctx, const esc_node_soa* nodes, int64_t lo, int64_t hi);
 /* Number of device-resident copies of the pod shard to rotate through on successive
@@ -646,8 +652,11 @@ int32_t esc_set_selections(esc_ctx* ctx, int32_t slack, int32_t group_cap);
  * of group g's nodes in idx (snapshot indices); idx == NULL (cap 0) fills which, offsets and
  * *n_total only (the size idx needs; ESC_E_LIMIT when cap is short).  world > 1: the rank's
  * own groups (the others ESC_SEL_NONE); a multi-device context: every group.  ESC_E_STATE
- * when selections are off; ESC_E_ORDER when the decision's ordering gave up (then use
- * esc_sort_nodes + esc_group_order). */
+ * when selections are off, and unless the last decision ran with them: none yet since
+ * esc_set_selections, esc_set_order_in_step or a reload (esc_load_pods / esc_load_nodes), or
+ * one decided with the ordering out of the step — ESC_SEL_NONE always means "the decision
+ * asks for no walk", never "not computed".  ESC_E_ORDER when the decision's ordering gave
+ * up (then use esc_sort_nodes + esc_group_order). */
 int32_t esc_selections(esc_ctx* ctx, int32_t* which, int64_t* offsets, int64_t* idx, int64_t cap, int64_t* n_total);
 
 /* ----------------------------------------------- per-function drop-ins (GPU)
