@@ -277,7 +277,8 @@ struct PodDev {
     const uint32_t* xp_base;   // [c_tiles + 1] extra-pair offset
     // K1 work plan (ensure_work): per workgroup up to K1_SEGS runs of one
     // class, {t0 | class << 48, t1} (t1 == 0: unused), balanced in work weight, at most two
-    // class boundaries per workgroup.  Null: the weight-range shares of variant 7.
+    // class boundaries per workgroup.  Null: plan_k1 could not place every class; K1 then
+    // walks equal weight ranges per workgroup and flushes whole rows.
     const int64_t* seg;
     // Compact K1 flush: workgroup b writes only the pod-slot columns its share
     // touches, wg_cols[b * n_col + i] = {column, destination} for i < wg_off[b] (n_col = the
@@ -395,13 +396,11 @@ enum WidePod : int { WP_CPU_LO = 0, WP_CPU_HI, WP_MEM_LO, WP_MEM_HI, WP_CNT, WP_
 enum TrkAcc : int { TA_CNT = 0, TA_CPU_LO, TA_CPU_HI, TA_MEM_LO, TA_MEM_HI, TA_K };
 
 // variant: 0 = the product K1 (512 threads: 8 waves per CU with up to 256 VGPRs, 3-4 K
-// tiles in flight per wave, one static share per workgroup); 3, 4, 9-14 = timing-only
-// ablations (wrong results), present in the measurement library only (ESC_K1_VARIANT,
-// scripts/k1_variants.py).
-// K1_CHUNKS: the unit of a static share's size bound (ensure_work); the K1 template's
-// dynamic-share form (a ticket of nblk * K1_CHUNKS chunks) is instantiated only by the
-// measurement library's ablations.
-constexpr int K1_CHUNKS = 4;
+// tiles in flight per wave, one static share per workgroup); 7 = the product kernel without
+// the plan (PodDev::seg null: the weight-range walk and the full-row flush, exact); 3, 4,
+// 9-13 = timing ablations (3, 4 exact; 9-13 wrong results), present in the measurement
+// library only.  The variant is chosen by ESC_K1_VARIANT, which only the measurement
+// library reads (scripts/k1_variants.py).
 struct DecCompact;
 // K1 diagnostics.  trace: per workgroup 8 words (esc_k1_trace; the share calibration reads words
 // 0-1): s_memrealtime (100 MHz) at start, after the K tiles, after the C tiles, after the
@@ -450,8 +449,7 @@ struct GroupList {
     int32_t first;
 };
 hipError_t launch_pod_reduce(const PodDev& p, const GroupDev& g, int32_t g0, int32_t gw, int nblk, int variant,
-                             uint64_t* part, int64_t* wide, uint32_t* ticket, int cap, const K1Diag& diag,
-                             hipStream_t st);
+                             uint64_t* part, int64_t* wide, const K1Diag& diag, hipStream_t st);
 hipError_t launch_pod_bigtiles(const PodDev& p, const GroupDev& g, const uint32_t* tiles, int64_t n_big,
                                int64_t* wide, hipStream_t st);
 // Compact decision record (32 B) that K3 / K4 write to pinned host memory each decision

@@ -556,7 +556,7 @@ __device__ __forceinline__ void k_sink(const KTile<R, NXP, 0>& T) {   // loads-o
 // accounting never waits early; the refills past the end go through the wave's run
 // descriptor at an offset past its size, which returns zeros without a memory access (they
 // used to re-read the slot's last tile: 1.2x K1's algorithmic fetch at 12.5 M pods).
-template <int R, int NXP, int PK, int NW, int ABLATE, int ST>
+template <int R, int NXP, int PK, int NW, int ABLATE>
 __device__ __forceinline__ void k_run(const PodDev& P, const GroupDev& G, const PodSink<ABLATE>& K,
                                       const PodClass& C, int64_t a, int64_t b, uint32_t lane) {
     constexpr int W = (int)k_tile_weight(R, NXP, PK);    // block size, half-KB units (generic: at most)
@@ -579,13 +579,13 @@ __device__ __forceinline__ void k_run(const PodDev& P, const GroupDev& G, const 
     KTile<R, NXP, PK> T[DS];
 #pragma unroll
     for (int d = 0; d < DS; ++d) {
-        k_load(rs, off(a + (int64_t)d * ST), lane, T[d], C);
+        k_load(rs, off(a + (int64_t)d * NW), lane, T[d], C);
         __builtin_amdgcn_sched_barrier(0);            // slots issue in order (see below)
     }
-    for (int64_t t = a; t < b; t += (int64_t)DS * ST) {
+    for (int64_t t = a; t < b; t += (int64_t)DS * NW) {
 #pragma unroll
         for (int d = 0; d < DS; ++d) {
-            const int64_t u = t + (int64_t)d * ST;
+            const int64_t u = t + (int64_t)d * NW;
             if (u < b) {                                       // wave-uniform
                 if constexpr (ABLATE & 32) k_sink(T[d]);
                 else k_process<R, NXP, ABLATE>(G, K, C, T[d]);
@@ -593,7 +593,7 @@ __device__ __forceinline__ void k_run(const PodDev& P, const GroupDev& G, const 
             // keep slot d's refill after its use: hoisting it would make the next slots'
             // waits count it (vmcnt is in order) and drain the pipeline
             __builtin_amdgcn_sched_barrier(0);
-            k_load(rs, off(u + (int64_t)DS * ST), lane, T[d], C);
+            k_load(rs, off(u + (int64_t)DS * NW), lane, T[d], C);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -901,9 +901,6 @@ __device__ __forceinline__ void tracker_entry(const NodeDev& N, const GroupDev& 
 // per-group partials stay in LDS and are flushed once.
 // ABLATE (timing-only builds): bit 0 LDS sink, bit 1 skip K tiles, bit 2 skip C tiles,
 // bit 5 loads only.
-// DYN: the K tiles' weight is cut into gridDim.x * K1_CHUNKS chunks taken from a ticket
-// counter (at most `cap` per workgroup), so workgroups that stream faster take more
-// and the launch does not wait on the slowest static share; DYN 0: one static share each.
 namespace {
 // ---- K4 decision helpers (k_node_groups' decide)
 // Exact total from split words; false when it is outside int64 (Quantity -> inf.Dec).
@@ -1020,14 +1017,16 @@ __host__ __device__ constexpr uint32_t k1_copy_words(uint32_t gw) { return (gw +
 __host__ __device__ constexpr uint32_t k1_reps(uint32_t gw) {
     return (uint64_t)k1_copy_words(gw) * 8 * K1_REPS <= K1_REP_LDS ? K1_REPS : 1u;
 }
-template <int THREADS, int ABLATE = 0, int DC = 3, int DYN = 0, int WS = 0>
+constexpr size_t k1_lds_bytes(uint32_t gw) {
+    return k1_reps(gw) > 1 ? (size_t)k1_reps(gw) * k1_copy_words(gw) * 8
+                           : (size_t)(gw + FC_COL - 1) / FC_COL * FC_COL * 2 * sizeof(uint64_t);
+}
+template <int THREADS, int ABLATE = 0, int DC = 3>
 __global__ __launch_bounds__(THREADS) void k_pod_reduce(PodDev P, GroupDev G, int32_t g0, uint32_t gw,
                                                         uint64_t* __restrict__ part,
-                                                        int64_t* __restrict__ wide,
-                                                        uint32_t* __restrict__ ticket, int cap, K1Diag FF) {
+                                                        int64_t* __restrict__ wide, K1Diag FF) {
     constexpr int NW = THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
-    __shared__ uint32_t s_chunk;
     uint64_t* const trace = FF.trace ? FF.trace + (int64_t)blockIdx.x * 8 : nullptr;
     if (trace && threadIdx.x == 0) {
         trace[0] = __builtin_amdgcn_s_memrealtime();
@@ -1058,22 +1057,12 @@ __global__ __launch_bounds__(THREADS) void k_pod_reduce(PodDev P, GroupDev G, in
     }
     const uint32_t lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // WS: every wave takes its own contiguous share of the K weight (a wave's restarts at
-    // class boundaries then idle only that wave, the WG's other waves keep streaming)
-    const int64_t n_chunks = DYN ? (int64_t)gridDim.x * K1_CHUNKS : (WS ? (int64_t)gridDim.x * NW : gridDim.x);
-    // every thread has read the previous ticket before thread 0 overwrites it
-    auto grab = [&]() -> int64_t {
-        __syncthreads();
-        if (threadIdx.x == 0) s_chunk = atomicAdd(ticket, 1u);
-        __syncthreads();
-        return (int64_t)__builtin_amdgcn_readfirstlane(s_chunk);
-    };
-    int64_t chunk = WS ? (int64_t)blockIdx.x * NW + wid : blockIdx.x;
-    if constexpr (DYN) chunk = grab();
-    else __syncthreads();
+    __syncthreads();                                     // the partials are zeroed
+#define ESC_KRUN(PK, RR, XX) \
+    case PK * 16 + RR * 4 + XX: k_run<RR, XX, PK, NW, ABLATE>(P, G, K, C, a, b, lane); break;
     // the host's work plan: this workgroup's class runs, every wave interleaved over each
     typedef __attribute__((address_space(4))) const int64_t ci64;
-    if (P.seg && !DYN && !WS && !(ABLATE & 2)) {
+    if (P.seg && !(ABLATE & 2)) {
         const ci64* sg = (const ci64*)P.seg + (int64_t)blockIdx.x * (2 * K1_SEGS);
         uint64_t n_runs = 0, run_w = 0;                  // diagnostics (trace[6], trace[7])
 #pragma unroll 1
@@ -1086,20 +1075,16 @@ __global__ __launch_bounds__(THREADS) void k_pod_reduce(PodDev P, GroupDev G, in
             const int64_t a = (t0c & ((1ll << 48) - 1)) + wid;
             if (a >= b) continue;
             switch (C.kind) {
-#define ESC_KRUN(PK, RR, XX) \
-    case PK * 16 + RR * 4 + XX: k_run<RR, XX, PK, NW, ABLATE, NW>(P, G, K, C, a, b, lane); break;
                 ESC_KRUN_ALL
-#undef ESC_KRUN
                 default: break;
             }
         }
-        chunk = n_chunks;                                // skip the weight-range walk
         if (trace && threadIdx.x == 0) { trace[6] = n_runs; trace[7] = run_w; }
-    }
-    for (int taken = 1; !(ABLATE & 2) && chunk < n_chunks; ++taken) {
-        // equal shares of work weight (bytes), not of tiles: a tile of a class with three
-        // container records streams ~3.4x the bytes of a simple one
-        const int64_t wl = P.k_weight * chunk / n_chunks, wh = P.k_weight * (chunk + 1) / n_chunks;
+    } else if (!(ABLATE & 2)) {
+        // no plan (plan_k1 could not place every class): equal shares of work weight (bytes),
+        // not of tiles: a tile of a class with three container records streams ~3.4x the
+        // bytes of a simple one
+        const int64_t wl = P.k_weight * blockIdx.x / gridDim.x, wh = P.k_weight * (blockIdx.x + 1) / gridDim.x;
         for (int ci = 0; ci < P.n_cls; ++ci) {
             const PodClass C = load_class(P.cls, ci);
             if (C.w0 >= wh) break;
@@ -1107,19 +1092,15 @@ __global__ __launch_bounds__(THREADS) void k_pod_reduce(PodDev P, GroupDev G, in
             const int64_t n = C.t1 - C.t0;
             const int64_t i0 = imin64(n, imax64(0, (wl - C.w0 + C.wt - 1) / C.wt));
             const int64_t i1 = imin64(n, imax64(0, (wh - C.w0 + C.wt - 1) / C.wt));
-            const int64_t a = C.t0 + i0 + (WS ? 0 : wid), b = C.t0 + i1;
+            const int64_t a = C.t0 + i0 + wid, b = C.t0 + i1;
             if (a >= b) continue;
             switch (C.kind) {
-#define ESC_KRUN(PK, RR, XX) \
-    case PK * 16 + RR * 4 + XX: k_run<RR, XX, PK, NW, ABLATE, (WS ? 1 : NW)>(P, G, K, C, a, b, lane); break;
                 ESC_KRUN_ALL
-#undef ESC_KRUN
                 default: break;
             }
         }
-        if (!DYN || taken >= cap) break;
-        chunk = grab();
     }
+#undef ESC_KRUN
     if (trace) {
         __syncthreads();
         if (threadIdx.x == 0) trace[1] = __builtin_amdgcn_s_memrealtime();
@@ -1221,50 +1202,33 @@ __global__ __launch_bounds__(THREADS) void k_pod_reduce(PodDev P, GroupDev G, in
         __syncthreads();
         if (threadIdx.x == 0) trace[3] = __builtin_amdgcn_s_memrealtime();
     }
-    if (DYN && threadIdx.x == 0) {
-        // every workgroup's last grab precedes its increment here: the last one resets
-        if (atomicAdd(ticket + 1, 1u) == gridDim.x - 1) {
-            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ticket + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
 }
 
 // ============================================================ K1 launchers by part
-// The K1 template is instantiated once per (variant, 16 record shapes): the production
-// variant in part 0 (with every other kernel) and the timing-only ablations in part 2, its
-// own translation unit, linked only into the measurement library (Makefile ABLATIONS=1,
-// libescalator_hip_measure.so).  The exact alternatives measured slower (1: two C tiles in
-// flight, 2: 1024 threads, 5: dynamic shares, 6: per-wave shares) were
-// removed from the product.
-#define ESC_K1(T, A, DC) ESC_K1D(T, A, DC, 0)
-#define ESC_K1D(T, A, DC, D) ESC_K1W(T, A, DC, D, 0)
-#define ESC_K1W(T, A, DC, D, W)                                                                       \
-    hipLaunchKernelGGL((k_pod_reduce<T, A, DC, D, W>), dim3(nblk), dim3(T), lds, st, p, g, g0, (uint32_t)gw, part, \
-                       wide, ticket, cap, diag)
+// The K1 template is instantiated once per (ABLATE, 16 record shapes): the product kernel
+// in part 0 (with every other kernel) and the timing-only ablations in part 2, its own
+// translation unit, linked only into the measurement library (Makefile ABLATIONS=1,
+// libescalator_hip_measure.so).
+#define ESC_K1(T, A, DC)                                                                                \
+    hipLaunchKernelGGL((k_pod_reduce<T, A, DC>), dim3(nblk), dim3(T), k1_lds_bytes((uint32_t)gw), st, p, g, g0, \
+                       (uint32_t)gw, part, wide, diag)
 #define ESC_K1_ARGS const PodDev &p, const GroupDev &g, int32_t g0, int32_t gw, int nblk, int variant, uint64_t *part, \
-                    int64_t *wide, uint32_t *ticket, int cap, const K1Diag &diag, hipStream_t st
+                    int64_t *wide, const K1Diag &diag, hipStream_t st
 hipError_t launch_pod_reduce_ablation(ESC_K1_ARGS) __attribute__((weak));
 
 #if ESC_PART == 0
 hipError_t launch_pod_reduce(ESC_K1_ARGS) {
-    const size_t lds = k1_reps((uint32_t)gw) > 1 ? (size_t)k1_reps((uint32_t)gw) * k1_copy_words((uint32_t)gw) * 8
-                                                 : (size_t)(gw + FC_COL - 1) / FC_COL * FC_COL * 2 * sizeof(uint64_t);
     switch (variant) {
-        case 0: ESC_K1(512, 0, 3); break;
+        case 0: case 7: ESC_K1(512, 0, 3); break;   // 7: the runtime passes no plan (pod_dev)
         default:                                  // timing-only ablations (measurement library only)
             if (!launch_pod_reduce_ablation) return hipErrorInvalidValue;
-            return launch_pod_reduce_ablation(p, g, g0, gw, nblk, variant, part, wide, ticket, cap, diag,
-                                              st);
+            return launch_pod_reduce_ablation(p, g, g0, gw, nblk, variant, part, wide, diag, st);
     }
     return hipGetLastError();
 }
 #elif ESC_PART == 2
 hipError_t launch_pod_reduce_ablation(ESC_K1_ARGS) {
-    const size_t lds = k1_reps((uint32_t)gw) > 1 ? (size_t)k1_reps((uint32_t)gw) * k1_copy_words((uint32_t)gw) * 8
-                                                 : (size_t)(gw + FC_COL - 1) / FC_COL * FC_COL * 2 * sizeof(uint64_t);
     switch (variant) {
-        case 14: ESC_K1W(512, 4 | 32, 3, 0, 1); break;   // per-wave shares, K tiles, loads only
         case 3: ESC_K1(512, 64, 3); break;       // <= 2 K tiles in flight per wave
         case 4: ESC_K1(512, 128, 3); break;      // <= 3 K tiles in flight per wave
         // Timing-only ablations (wrong results; scripts/k1_variants.py), see k_pod_reduce.
@@ -1279,8 +1243,6 @@ hipError_t launch_pod_reduce_ablation(ESC_K1_ARGS) {
 }
 #endif
 #undef ESC_K1
-#undef ESC_K1D
-#undef ESC_K1W
 #undef ESC_K1_ARGS
 
 #if ESC_PART == 0

@@ -184,7 +184,6 @@ struct esc_ctx {
     uint64_t* d_ttrace = nullptr;                             // tail + node-groups block timestamps
     int64_t ttrace_cap = 0, ttrace_tail = 0, ttrace_ng = 0;   // words; blocks of the last traced step
     int64_t* d_wide_pod = nullptr;
-    uint32_t* d_k1_ticket = nullptr;                          // K1 dynamic shares (next chunk, done)
     int64_t* d_k1seg = nullptr;                               // K1 work plan [nblk][K1_SEGS][2]
     // Compact K1 flush: the pod-slot columns each workgroup's share touches
     // (bitmap of touch_tw u32 per workgroup, kept current by pod upserts), as per-workgroup
@@ -199,7 +198,6 @@ struct esc_ctx {
     uint32_t* d_wg_off = nullptr;
     uint32_t* d_col_rows = nullptr;
     std::vector<double> k1_share;                             // calibrated K1 shares (esc_k1_calibrate)
-    int k1_cap = 0;                                           // K1 chunks per workgroup at most (0: static)
     uint64_t* d_k1_trace = nullptr;                           // K1 per-workgroup timestamps (esc_k1_trace)
     int64_t* d_trk_acc = nullptr;                             // [G][TA_K] dry-mode tracked sums
     int64_t* d_pwords = nullptr;                              // active exchange buffer [world * own_cap][PW_K]
@@ -484,8 +482,7 @@ PodDev pod_dev(const esc_ctx* c, int replica) {
     p.xc_cpu = b.xc_cpu; p.xc_mem = b.xc_mem; p.xp = b.xp;
     p.xc_base = b.xc_base; p.xp_base = b.xp_base;
     p.cls = b.cls;
-    p.seg = (c->k1_variant == 5 || c->k1_variant == 6 || c->k1_variant == 7 || c->k1_variant == 14) ? nullptr
-                                                                                                    : c->d_k1seg;
+    p.seg = c->k1_variant == 7 ? nullptr : c->d_k1seg;   // 7: the product kernel's no-plan walk
     p.wg_cols = c->touch_on ? c->d_wg_cols : nullptr;
     p.wg_off = c->touch_on ? c->d_wg_off : nullptr;
     p.n_cls = c->n_cls;
@@ -620,7 +617,7 @@ int32_t replay_step(esc_ctx* c, std::vector<hipGraphExec_t>& gs, int r, bool dec
 }
 
 void release_work(esc_ctx* c) {
-    dfree(c->d_k1seg); dfree(c->d_pod_part); dfree(c->d_wide_pod); dfree(c->d_k1_ticket); dfree(c->d_trk_acc);
+    dfree(c->d_k1seg); dfree(c->d_pod_part); dfree(c->d_wide_pod); dfree(c->d_trk_acc);
     dfree(c->d_k1_trace);
     dfree(c->d_ttrace);
     c->ttrace_cap = 0;
@@ -1110,7 +1107,7 @@ int32_t touch_upload(esc_ctx* c) {
 
 // (Re)computes the touched columns of the current K1 plan (after ensure_work and every plan
 // change of esc_k1_calibrate): k_touch on the device, the lists on the host.  Off (every
-// row flushed whole) without a static plan (dynamic shares) or with ESC_K1_FULL_FLUSH.
+// row flushed whole) without a static plan or with ESC_K1_FULL_FLUSH.
 int32_t touch_refresh(esc_ctx* c, const std::vector<int64_t>& plan) {
     const PodDev p0 = pod_dev(c, 0);
     const bool on = !plan.empty() && p0.seg && !c->full_flush && c->nblk > 0 && !c->pods.empty();
@@ -1199,24 +1196,21 @@ int32_t ensure_work(esc_ctx* c) {
     const int64_t S = pod_slots(c);
     const int gw = (int)std::min<int64_t>(S, POD_WINDOW_MAX);
     const int lds = (gw + FC_COL - 1) / FC_COL * FC_COL * 16;   // K1's two LDS halves, whole columns each
-    const int max_blocks = c->k1_variant == 2 ? 2 : 4;   // 2048 threads per CU
-    const int per_cu = std::max(1, std::min(max_blocks, LDS_BYTES / std::max(lds, 1)));
+    const int per_cu = std::max(1, std::min(4, LDS_BYTES / std::max(lds, 1)));   // 2048 threads per CU
     int64_t nblk = c->cu_count * per_cu;
     // every workgroup takes 1/nblk of the K tiles' weight + ceil(c_tiles/nblk) C tiles;
     // keep that within PODS_PER_BLOCK_MAX (exactness of the packed LDS partials)
-    int64_t cap = 0;
+    // A deliberately loose pre-bound (a share counted as LOOSE quarter shares, each with its
+    // own partial tile per class); plan_worst below does the exact check.  Tightening it
+    // would change nblk, and with it K1's speed and the LDS partials' exactness margin.
+    constexpr int64_t LOOSE = 4;
     auto block_pods = [&](int64_t b) {
-        // a weight share holds at most share / (lightest tile weight) + one partial tile
-        // per class; with dynamic shares a workgroup takes up to K1_CHUNK_CAP chunks of
-        // 1 / (b * K1_CHUNKS) each
-        const int64_t nch = b * K1_CHUNKS;
-        return cap * ((c->k_weight + nch - 1) / nch / K_TILE_WEIGHT_MIN + c->n_cls + 1) * TILE +
+        // a weight share holds at most share / (lightest tile weight) + one partial tile per class
+        const int64_t nch = b * LOOSE;
+        return LOOSE * ((c->k_weight + nch - 1) / nch / K_TILE_WEIGHT_MIN + c->n_cls + 1) * TILE +
                ((c->c_tiles + b - 1) / b) * CTILE;
     };
-    // the static share (cap K1_CHUNKS: one share) sets the grid
-    cap = K1_CHUNKS;
     while (block_pods(nblk) > PODS_PER_BLOCK_MAX) nblk *= 2;
-    c->k1_cap = 0;
     nblk = std::min<int64_t>(nblk, std::max(c->k_tiles, c->c_tiles));
     std::vector<int64_t> plan;
     for (;;) {            // the plan's own per-workgroup pod counts must keep the LDS words exact
@@ -1236,8 +1230,6 @@ int32_t ensure_work(esc_ctx* c) {
     const int64_t SP = slot_stride(c), n_col = SP / FC_COL;
     HIP_TRY(dalloc(&c->d_pod_part, (size_t)std::max<int64_t>(nblk, 1) * 2 * SP));
     HIP_TRY(dalloc(&c->d_wide_pod, (size_t)S * WP_K));
-    HIP_TRY(dalloc(&c->d_k1_ticket, 2));
-    HIP_TRY(hipMemset(c->d_k1_ticket, 0, 2 * sizeof(uint32_t)));
     HIP_TRY(hipMemset(c->d_wide_pod, 0, (size_t)S * WP_K * sizeof(int64_t)));
     HIP_TRY(dalloc(&c->d_trk_acc, (size_t)G * TA_K));
     HIP_TRY(hipMemset(c->d_trk_acc, 0, (size_t)G * TA_K * sizeof(int64_t)));
@@ -1310,6 +1302,18 @@ int32_t stage_mark(esc_ctx* c) {
     return ESC_OK;
 }
 
+// Every K1 launch of a step on replica r: the pod pass over each LDS window of pod slots,
+// then the big C tiles.
+int32_t launch_k1(esc_ctx* c, int r, const GroupDev& g, uint64_t* trace, hipStream_t st) {
+    const PodDev p = pod_dev(c, r);
+    const int32_t S = (int32_t)pod_slots(c);
+    for (int32_t g0 = 0; g0 < S; g0 += POD_WINDOW_MAX)
+        HIP_TRY(launch_pod_reduce(p, g, g0, std::min(POD_WINDOW_MAX, S - g0), c->nblk, c->k1_variant, c->d_pod_part,
+                                  c->d_wide_pod, K1Diag{trace}, st));
+    HIP_TRY(launch_pod_bigtiles(p, g, c->pods[r].big, c->n_big, c->d_wide_pod, st));
+    return ESC_OK;
+}
+
 int32_t enqueue_step(esc_ctx* c, int r, bool decide, bool copy_out) {
     const GroupDev g = group_dev(c);
     const NodeDev n = node_dev(c);
@@ -1326,15 +1330,7 @@ int32_t enqueue_step(esc_ctx* c, int r, bool decide, bool copy_out) {
     if (c->force_wide) {
         if (c->k_tiles + c->c_tiles) HIP_TRY(launch_wide_pods(pod_dev(c, r), g, c->d_wide_pod, st));
     } else if (c->nblk) {
-        const PodDev p = pod_dev(c, r);
-        const int32_t S = (int32_t)pod_slots(c);
-        for (int32_t g0 = 0; g0 < S; g0 += POD_WINDOW_MAX) {           // LDS windows of pod slots
-            const int32_t gw = std::min(POD_WINDOW_MAX, S - g0);
-            const K1Diag diag{c->d_k1_trace};
-            HIP_TRY(launch_pod_reduce(p, g, g0, gw, c->nblk, c->k1_variant, c->d_pod_part, c->d_wide_pod,
-                                      c->d_k1_ticket, c->k1_cap, diag, st));
-        }
-        HIP_TRY(launch_pod_bigtiles(p, g, c->pods[r].big, c->n_big, c->d_wide_pod, st));
+        if (int32_t rc = launch_k1(c, r, g, c->d_k1_trace, st)) return rc;
         nblk = c->nblk;
     }
     if (int32_t rc = mark()) return rc;
@@ -2427,7 +2423,6 @@ int32_t esc_k1_time(esc_ctx* c, int32_t reps, double* ms_per_launch) {
     hipSetDevice(c->device);
     hipStream_t st = c->stream;
     const GroupDev g = group_dev(c);
-    const int32_t S = (int32_t)pod_slots(c);
     const int nrep = (int)c->pods.size();
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipEventRecord(c->k1t_ev[0], st));
@@ -2437,16 +2432,8 @@ int32_t esc_k1_time(esc_ctx* c, int32_t reps, double* ms_per_launch) {
     // the 256 MB Infinity Cache, launched on one replica back to back, is read from the
     // cache, not HBM (round 5, a rank of 8's 124 MB: 29.7-30.0 us on one replica, 30.7-31.1
     // rotating)
-    for (int32_t k = 0; k < reps; ++k) {
-        const int r = (c->cur + k) % nrep;
-        const PodDev p = pod_dev(c, r);
-        for (int32_t g0 = 0; g0 < S; g0 += POD_WINDOW_MAX) {
-            const K1Diag diag{nullptr};
-            HIP_TRY(launch_pod_reduce(p, g, g0, std::min(POD_WINDOW_MAX, S - g0), c->nblk, c->k1_variant, c->d_pod_part,
-                                      c->d_wide_pod, c->d_k1_ticket, c->k1_cap, diag, st));
-        }
-        HIP_TRY(launch_pod_bigtiles(p, g, c->pods[r].big, c->n_big, c->d_wide_pod, st));
-    }
+    for (int32_t k = 0; k < reps; ++k)
+        if ((rc = launch_k1(c, (c->cur + k) % nrep, g, nullptr, st))) return rc;
     HIP_TRY(hipEventRecord(c->k1t_ev[1], st));
     // the exact-path accumulators K1 added to without a fold: back to zero for the next step
     HIP_TRY(hipMemsetAsync(c->d_wide_pod, 0, (size_t)pod_slots(c) * WP_K * sizeof(int64_t), st));

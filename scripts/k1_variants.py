@@ -12,7 +12,7 @@ import numpy as np  # noqa: E402
 cfg = int(os.environ.get("CFG", 4))
 P, N, G = {4: (100_000_000, 1_000_000, 10_000), 2: (1_000_000, 10_000, 100), 3: (10_000_000, 100_000, 100)}[cfg]
 P = int(os.environ.get("PODS", P))            # a rank's shard at N > 1 (fixed-cost study)
-variants = [int(v) for v in os.environ.get("VARIANTS", "0,2,9,10,11").split(",")]
+variants = [int(v) for v in os.environ.get("VARIANTS", "0,9,10,11").split(",")]
 rounds = int(os.environ.get("ROUNDS", 3))
 import escalator_amd as esc  # noqa: E402
 

@@ -1,8 +1,9 @@
 """Child process of tests/test_gpu_faults.py: one forced-failure scenario on the MEASUREMENT
 library (ESC_LIB_PATH=escalator_amd/libescalator_hip_measure.so, whose esc_debug_* entry
 points inject the failures; the product library has none), printing one JSON line of what
-it observed.  Run in its own process so the product library of the parent test process and
-this one never share a process."""
+it observed.  Also K1's no-plan walk (tests/test_gpu_slots.py), which only that library's
+ESC_K1_VARIANT knob reaches deterministically.  Run in its own process so the product
+library of the parent test process and this one never share a process."""
 import ctypes as C
 import json
 import os
@@ -140,10 +141,47 @@ def mode_patch(lib):
     return out
 
 
+def mode_noplan(lib, synth_groups):
+    """K1 without a work plan (ESC_K1_VARIANT=7 hands the product kernel a null plan, the path
+    a snapshot takes whose classes plan_k1 cannot place): equal weight ranges per workgroup and
+    the full-row flush.  Two contexts of random objects (several K record shapes, some C
+    pods): about 40 groups in one LDS window, then the generator's `synth_groups` groups, whose
+    last pod slot (the default filter's) is a second window of its own."""
+    import random
+    from randobj import make_groups, make_nodes, make_pods, make_states
+    assert os.environ.get("ESC_K1_VARIANT") == "7"
+    rng = random.Random(7007)
+    s = esc.Synth(1000, 100, synth_groups, config=4, seed=0xE5CA1A7E00000004)   # its groups and states only
+    out = {}
+    for tag, groups, states in (("small", make_groups(rng, 40), make_states(rng, 40)), ("two_windows", s.groups, s.states)):
+        ctx = esc.Context(groups)
+        P, N = ctx.pack(make_pods(rng, 4000, groups), make_nodes(rng, 300, groups))
+        f = P["flags"].astype(np.uint64)
+        rec, nxp = ((f >> 8) & 0xFF) + ((f >> 16) & 0xFF) + ((f >> 4) & 1), (f >> 24) & 0x3F
+        in_c = (rec > 3) | (nxp > 3)                              # C tiles; the others K tiles by shape
+        ctx.load(P, N)
+        ctx.set_state(states)
+        ok = True
+        for _ in range(2):
+            ctx.run()
+            ok &= exact(ctx, P, N, groups, states)
+        tr = ctx.k1_trace()
+        entries, full = ctx.k1_flush_entries()
+        out[tag] = {"slots": lib.esc_ctx_num_group_pairs(ctx.handle) + 1, "exact": ok, "entries": entries, "full": full,
+                    "workgroups": int(tr.shape[0]), "trace_live": bool(np.all(tr[:, 0] != 0)),
+                    "plan_words_zero": bool(np.all(tr[:, 6:8] == 0)), "c_pods": int(in_c.sum()),
+                    "k_shapes": len(set(zip(rec[~in_c].tolist(), nxp[~in_c].tolist())))}
+    return out
+
+
+
 if __name__ == "__main__":
     lib = L.load()
     assert hasattr(lib, "esc_debug_lookback_fail"), "not the measurement library: %s" % L.LIB_PATH
     lib.esc_debug_lookback_fail.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.esc_debug_fail_patches.argtypes = [C.c_void_p, C.c_int32]
-    res = {"order": mode_order, "listing": mode_listing, "patch": mode_patch}[sys.argv[1]](lib)
+    if sys.argv[1] == "noplan":
+        res = mode_noplan(lib, int(sys.argv[2]))
+    else:
+        res = {"order": mode_order, "listing": mode_listing, "patch": mode_patch}[sys.argv[1]](lib)
     print(json.dumps(res), flush=True)

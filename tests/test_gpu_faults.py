@@ -25,10 +25,10 @@ MEASURE = os.path.join(ROOT, "escalator_amd", "libescalator_hip_measure.so")
 ESC_E_HIP, ESC_E_STATE, ESC_E_ORDER = -2, -5, -8
 
 
-def run_child(mode):
+def run_child(mode, *args, **env):
     assert os.path.exists(MEASURE), "build the measurement library: make -C escalator_amd/csrc ABLATIONS=1"
-    env = dict(os.environ, ESC_LIB_PATH=MEASURE)
-    r = subprocess.run([sys.executable, "-u", os.path.join(HERE, "fault_child.py"), mode], capture_output=True,
+    env = dict(os.environ, ESC_LIB_PATH=MEASURE, **env)
+    r = subprocess.run([sys.executable, "-u", os.path.join(HERE, "fault_child.py"), mode, *args], capture_output=True,
                        text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

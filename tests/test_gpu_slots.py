@@ -159,6 +159,26 @@ def test_window_edges(esc, S):
             check_against_c_oracle(*ctx.results(), otot, odf, odi)
 
 
+# ------------------------------------------------------------------ K1 without a work plan
+def test_no_plan_walk_full_row_flush():
+    """The walk K1 takes when plan_k1 places no plan (PodDev::seg null): equal weight ranges
+    per workgroup, every row flushed whole.  ESC_K1_VARIANT=7 on the measurement library runs
+    the product kernel that way (a child process, tests/fault_child.py): ~40 groups in one
+    window, then S = WINDOW + 1, whose second window is the default filter's slot alone (the
+    full-row flush at g0 > 0).  Bit-exact against the C oracle; no compact flush; trace words
+    6-7, which only the plan branch writes, stay zero in every workgroup."""
+    from test_gpu_faults import run_child
+    S = WINDOW + 1
+    assert windows(S) == [(0, WINDOW), (WINDOW, 1)]
+    r = run_child("noplan", str(synth_groups_for_slots(S)), ESC_K1_VARIANT="7")
+    assert 30 <= r["small"]["slots"] <= 42 and r["two_windows"]["slots"] == S, r
+    for c in r.values():
+        assert c["k_shapes"] >= 3 and c["c_pods"] > 0 and c["workgroups"] > 1, r     # what the input holds
+        assert c["exact"], r
+        assert c["entries"] == c["full"] > 0, r
+        assert c["trace_live"] and c["plan_words_zero"], r
+
+
 # ------------------------------------------------ pods that straddle windows, from objects
 def _pair_sets(P):
     """(lowest, highest) selected pair of every packed pod (NONE, -1 without any)."""
