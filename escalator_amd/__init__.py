@@ -8,6 +8,8 @@ Python host over that ABI, mirroring the reference's interfaces:
 * ``escalator_amd.controller`` — pkg/controller (calcPercentUsage, calcScaleUpDelta,
   taintOldestN, untaintNewestN, scaleNodeGroup over every group at once)
 * ``escalator_amd.context``    — the device snapshot + batched decision
+* ``escalator_amd.events``     — the informer cache in front of the resident snapshot: identity
+  maps, pod ids, batched event flushes, one reload on ESC_E_LIMIT (pkg/k8s/cache.go)
 * ``escalator_amd.dist``       — one process per GPU, sharded snapshot, RCCL exchange
 
 Importing the package loads the library and raises if it has not been built.

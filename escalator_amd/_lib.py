@@ -174,6 +174,7 @@ _SIGS = {
     "esc_tracker_update": (i32, [VP, i32, P(i64), i64, P(i64), i64]),
     "esc_tracker_list": (i32, [VP, i32, P(i64), i64, P(i64)]),
     "esc_load_placement": (i32, [VP, P(u32), P(i64), P(C.c_uint8)]),
+    "esc_nodes_facts": (i32, [VP, P(i64), i64, P(i64), P(C.c_uint8)]),
     "esc_try_remove": (i32, [VP, i64, P(i64), P(i64), P(Removal)]),
     "esc_pods_bind": (i32, [VP, P(i64), P(u32), i64]),
     "esc_reap_occupancy": (i32, [VP]),

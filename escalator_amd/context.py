@@ -494,6 +494,18 @@ class Context:
                                             t.ctypes.data_as(C.POINTER(C.c_int64)),
                                             nd.ctypes.data_as(C.POINTER(C.c_uint8))), "esc_load_placement")
 
+    def nodes_facts(self, ids, taint_s, no_delete):
+        """The escalator-taint time (Unix s, INT64_MIN = none) and no-delete flag of the nodes
+        `ids` alone, in place (esc_nodes_facts): bindings and occupancy stay."""
+        ids = np.ascontiguousarray(ids, np.int64)
+        t = np.ascontiguousarray(taint_s, np.int64)
+        nd = np.ascontiguousarray(no_delete, np.uint8)
+        if not len(ids) == len(t) == len(nd):
+            raise ValueError("nodes_facts: ids, taint_s and no_delete differ in length")
+        L.check(self.lib.esc_nodes_facts(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids),
+                                         t.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         nd.ctypes.data_as(C.POINTER(C.c_uint8))), "esc_nodes_facts")
+
     def try_remove(self, now_ns: int, soft_ns, hard_ns) -> np.ndarray:
         """TryRemoveTaintedNodes for every group: (n_candidates, n_delete, pods_remaining)."""
         s_ = np.ascontiguousarray(np.broadcast_to(np.asarray(soft_ns, np.int64), (self.G,)))

@@ -6,6 +6,8 @@
   (GPU radix sort; every taint/untaint succeeds, i.e. the dry-mode walk).
 * ``Controller`` — (*Controller).RunOnce (controller.go:400) over every group in ONE
   batched decision: listers -> K0 packer -> HIP reduce -> K4 decide.
+* ``ResidentController`` — the same RunOnce on the snapshot that stays on the device, fed by
+  informer events through ``events.EventQueue`` instead of re-listing and reloading per scan.
 """
 from __future__ import annotations
 
@@ -275,7 +277,11 @@ class Controller:
         soft = [int(grp.get("soft_delete_grace_ns", 0)) for grp in self.groups]
         hard = [int(grp.get("hard_delete_grace_ns", 0)) for grp in self.groups]
         self._removal = self.ctx.try_remove(now, soft, hard)
-        names = [n.get("name", "") for n in nodes]
+        return self._act(tot, dec, [n.get("name", "") for n in nodes])
+
+    def _act(self, tot, dec, names) -> list[dict]:
+        """The per-group action switch of one scan (controller.go:265-383) over the decision
+        `tot` / `dec` and self._sel / self._removal; names[j] = the name of snapshot node j."""
         out = []
         for g in range(len(self.groups)):
             d = dec[g]
@@ -314,3 +320,75 @@ class Controller:
         g = next(i for i, s in enumerate(self.groups) if s["name"] == name)
         r = self.run_once(list_pods, list_nodes)[g]
         return r["delta"], r["err"]
+
+
+class _NodeNames:
+    """names[j] for the walks, over the queue's index -> name map."""
+
+    def __init__(self, events):
+        self._events = events
+
+    def __getitem__(self, j):
+        return self._events.node_name(j)
+
+
+class ResidentController(Controller):
+    """RunOnce on the resident snapshot: no listers, no reload per scan.
+
+    The caller feeds informer events to ``.events`` (escalator_amd/events.py: ``pod_add`` /
+    ``pod_update`` / ``pod_delete``, ``node_add`` / ``node_update`` / ``node_delete``);
+    ``run_once()`` flushes them into the device snapshot as batched patches (one reload when
+    the ``spare`` room runs out), then decides, reaps and acts exactly as ``Controller`` does —
+    the same host state, the same per-group result records, the same action switch.  Node
+    indices handed to the actuator and returned in the records are snapshot indices
+    (``events.node_name(j)`` names them).
+
+    Wet mode: the actuator's taint / untaint / delete_nodes are API writes; the node Update or
+    Delete they cause comes back as events the caller feeds to ``.events`` — the controller
+    does not patch the snapshot behind the queue's back.  Dry mode: ``taint_tracker[g]`` stays
+    the list of names (controller.go:35) and is mirrored onto the device with
+    ``tracker_update`` after the walks; after a flush that added nodes or reloaded, tracked
+    names the device does not track (a reload drops the tracker, a node back under a tracked
+    name has a new index) are re-added; a tracked name whose node is gone stays in the list."""
+
+    def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
+                 selection_slack: int = 4, spare: float = 0.5):
+        super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
+                         selection_slack=selection_slack)
+        from .events import EventQueue
+        self.spare = float(spare)
+        self.events = EventQueue(spare=self.spare)
+
+    def _sync_trackers(self):
+        """filterNodes reads the tracker by name (controller.go:126-138): every tracked name
+        with a live node is tracked on the device."""
+        for g, names in self.taint_tracker.items():
+            if not names:
+                continue
+            want = {self.events.node_index(n) for n in names} - {None}
+            missing = sorted(want - set(int(j) for j in self.ctx.tracker_list(g)))
+            if missing:
+                self.ctx.tracker_update(g, add=missing)
+
+    def run_once(self) -> list[dict]:
+        self.events.flush(self.ctx)
+        if self.events.touched_nodes:
+            self._sync_trackers()
+        now = self.clock()
+        self._lock_states(now)
+        tot, dec = self.ctx.decide_all(self.state)       # the ordering is in the step
+        try:
+            self._sel = self.ctx.selections()
+        except L.EscError as e:
+            if e.code != L.ESC_E_ORDER:
+                raise
+            self._sel = None
+            self.ctx.sort_nodes()
+        soft = [int(grp.get("soft_delete_grace_ns", 0)) for grp in self.groups]
+        hard = [int(grp.get("hard_delete_grace_ns", 0)) for grp in self.groups]
+        self._removal = self.ctx.try_remove(now, soft, hard)
+        out = self._act(tot, dec, _NodeNames(self.events))
+        for g, r in enumerate(out):                      # the dry-mode walks' tracker changes
+            if self.groups[g]["dry_mode"] and (r.get("tainted_now") or r.get("untainted_now")):
+                self.ctx.tracker_update(g, add=r.get("tainted_now", []), remove=r.get("untainted_now", []))
+        return out

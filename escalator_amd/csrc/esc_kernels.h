@@ -551,6 +551,9 @@ struct PatchTargets {          // k_patch destinations: 4-byte arrays 0-5, 8-byt
     uint16_t* u16[2];
 };
 hipError_t launch_patch(const PatchTargets& t, const uint64_t* where, const uint64_t* what, int64_t n, hipStream_t st);
+// esc_nodes_facts: node ids[i]'s taint time and no-delete byte, one event per thread (ids unique).
+hipError_t launch_node_facts(int64_t* taint_s, uint8_t* no_delete, const int64_t* ids, const int64_t* ev_taint,
+                             const uint8_t* ev_nd, int64_t n, hipStream_t st);
 
 
 // Ordering (K5), see esc_kernels.hip: the age index (once per snapshot) and the per-decision

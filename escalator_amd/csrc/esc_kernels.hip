@@ -2982,6 +2982,20 @@ __global__ __launch_bounds__(256) void k_patch(PatchTargets T, const uint64_t* _
     else T.u16[t - 12][idx] = (uint16_t)what[i];
 }
 
+// Per-node reaping facts in place (esc_nodes_facts): event i gives table slot ids[i] its
+// escalator-taint time and its no-delete byte.  The host refuses a batch with a repeated id,
+// so every element has one writer; neighbouring bytes of no_delete are byte stores of their
+// own (no read-modify-write of the word around them).
+__global__ __launch_bounds__(256) void k_node_facts(int64_t* __restrict__ taint_s, uint8_t* __restrict__ no_delete,
+                                                    const int64_t* __restrict__ ids, const int64_t* __restrict__ ev_taint,
+                                                    const uint8_t* __restrict__ ev_nd, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = ids[i];
+    taint_s[j] = ev_taint[i];
+    no_delete[j] = ev_nd[i] ? 1 : 0;
+}
+
 // ===================================================================== scale-down reaping
 // §8f rank 2: TryRemoveTaintedNodes (scale_down.go:51-136) for every group.
 namespace {
@@ -3257,6 +3271,14 @@ hipError_t launch_try_remove(const NodeDev& n, const GroupDev& g, const RemovalD
 hipError_t launch_patch(const PatchTargets& t, const uint64_t* where, const uint64_t* what, int64_t n, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_patch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t, where, what, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_node_facts(int64_t* taint_s, uint8_t* no_delete, const int64_t* ids, const int64_t* ev_taint,
+                             const uint8_t* ev_nd, int64_t n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_node_facts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, taint_s, no_delete, ids,
+                       ev_taint, ev_nd, n);
     return hipGetLastError();
 }
 

@@ -63,6 +63,7 @@ int32_t multi_pods_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_pods_bind(esc_ctx* c, const int64_t* ids, const uint32_t* pod_node, int64_t n);
 int32_t multi_nodes_update(esc_ctx* c, const int64_t* ids, int64_t n, const uint32_t* flags, const int64_t* cpu,
                            const int64_t* mem);
+int32_t multi_nodes_facts(esc_ctx* c, const int64_t* ids, int64_t n, const int64_t* taint_s, const uint8_t* no_delete);
 int32_t multi_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out);
 int32_t multi_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s);

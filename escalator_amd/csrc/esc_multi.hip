@@ -452,6 +452,10 @@ int32_t multi_nodes_update(esc_ctx* c, const int64_t* ids, int64_t n, const uint
     return node_event(c, [&](int i) { return esc_nodes_update(M(c).subs[i], ids, n, flags, cpu, mem); });
 }
 
+int32_t multi_nodes_facts(esc_ctx* c, const int64_t* ids, int64_t n, const int64_t* taint_s, const uint8_t* no_delete) {
+    return node_event(c, [&](int i) { return esc_nodes_facts(M(c).subs[i], ids, n, taint_s, no_delete); });
+}
+
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s) {
     if (M(c).diverged) return ESC_E_STATE;
     if (int32_t rc = nodes_relabel_check(M(c).subs[0], ids, s)) return rc;   // nothing applied anywhere

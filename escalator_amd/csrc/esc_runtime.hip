@@ -4492,6 +4492,47 @@ int32_t esc_load_placement(esc_ctx* c, const uint32_t* pod_node, const int64_t* 
     return ESC_OK;
 }
 
+// esc_nodes_facts: the same per-node facts for a handful of nodes (a node Update that taints
+// a node or changes its no-delete annotation, or a node just added), in place: the batch is
+// staged with one copy — ids, taint times, then the no-delete bytes — and scattered by one
+// launch.  Bindings and occupancy do not depend on the facts and stay.
+int32_t esc_nodes_facts(esc_ctx* c, const int64_t* ids, int64_t n, const int64_t* taint_s, const uint8_t* no_delete) {
+    if (c && c->multi) return esc::multi_nodes_facts(c, ids, n, taint_s, no_delete);
+    if (!c || n < 0 || (n > 0 && (!ids || !taint_s || !no_delete))) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->node_removal || !c->d_taint_s || !c->d_no_delete) return ESC_E_STATE;
+    if (n == 0) return ESC_OK;
+    for (int64_t i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= c->n_nodes || ids[i] >= c->rm_nodes || (c->h_nflags[ids[i]] & ESC_NF_ABSENT))
+            return ESC_E_INVAL;
+    {
+        std::vector<int64_t> seen(ids, ids + n);           // one event per node: every element has one writer
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return ESC_E_INVAL;
+    }
+    hipSetDevice(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<uint8_t> stage((size_t)n * 17);
+    std::memcpy(stage.data(), ids, (size_t)n * 8);
+    std::memcpy(stage.data() + (size_t)n * 8, taint_s, (size_t)n * 8);
+    std::memcpy(stage.data() + (size_t)n * 16, no_delete, (size_t)n);
+    uint8_t* d = nullptr;
+    HIP_TRY(dalloc(&d, stage.size()));
+    if (hipMemcpy(d, stage.data(), stage.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(d);                                          // nothing written yet: not stale
+        return ESC_E_HIP;
+    }
+    c->rm_valid = false;
+    return guarded(c, STALE_NODES, [&]() -> int32_t {
+        hipError_t e = launch_node_facts(c->d_taint_s, c->d_no_delete, reinterpret_cast<const int64_t*>(d),
+                                         reinterpret_cast<const int64_t*>(d) + n, d + (size_t)n * 16, n, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        dfree(d);
+        HIP_TRY(e);
+        return ESC_OK;
+    });
+}
+
 // K6 (node occupancy by group filter over this rank's pods) — the first half of
 // esc_try_remove; with several ranks the occupancy words are summed across ranks before K7.
 int32_t esc_reap_occupancy(esc_ctx* c) {

@@ -1,0 +1,289 @@
+"""The informer cache in front of the resident snapshot: identities -> snapshot indices.
+
+``EventQueue`` plays the reference's informer cache feeding the listers
+(pkg/k8s/cache.go:16-56, pod_listers.go:33-49, node_listers.go:33-48) plus the identity
+maps the event calls of the C ABI need: every ``esc_pods_*`` / ``esc_nodes_*`` call takes
+snapshot indices, and this queue is what maps a pod key or a node name to one, hands out and
+recycles pod ids, batches a scan's events into at most one call per kind and falls back to
+one full reload when ``ESC_E_LIMIT`` says the spare room ran out.
+
+It holds the current objects (plain-dict records, escalator_amd/objects.py) — the truth a
+reload is built from — and, beside them, what the device last saw of each.  Ingest
+(``pod_add`` ... ``node_delete``) only changes the object store and marks the key dirty;
+``flush(ctx)`` diffs the dirty keys against the device's view, so events on one key coalesce
+(the last write wins, an add and a delete of a key the device never saw cancel) without a
+log.  Records are values: an update hands in a new dict, it does not change the one the
+queue holds.  ``ctx`` is anything with ``Context``'s methods.
+"""
+from __future__ import annotations
+
+import heapq
+
+import numpy as np
+
+from ._lib import ESC_E_LIMIT
+from .objects import NO_DELETE_ANNOTATION, TO_BE_REMOVED_KEY, placement, taint_time
+
+NONE = 0xFFFFFFFF
+KINDS = ("nodes_delete", "nodes_add", "nodes_relabel", "nodes_update", "nodes_facts",
+         "pods_delete", "pods_upsert", "pods_bind")
+# the pod fields the packed record is built from (objects.pods_to_c)
+_POD_SPEC = ("owner_kinds", "node_selector", "affinity", "containers", "init_containers", "overhead")
+
+
+class _Reload(Exception):
+    """A batched call answered ESC_E_LIMIT: the rest of the batch is abandoned."""
+
+
+def pod_key(pod: dict) -> str:
+    ns = pod.get("namespace")
+    return "%s/%s" % (ns, pod.get("name", "")) if ns else pod.get("name", "")
+
+
+def _pod_spec(p: dict):
+    src = (p.get("annotations") or {}).get("kubernetes.io/config.source")
+    return [p.get(k) or None for k in _POD_SPEC] + [src]
+
+
+def _no_delete(n: dict) -> int:
+    return 1 if (n.get("annotations") or {}).get(NO_DELETE_ANNOTATION, "") else 0
+
+
+def _facts(n: dict):
+    return taint_time(n), _no_delete(n)
+
+
+def _shape(n: dict):
+    """What esc_nodes_relabel carries beyond esc_nodes_update."""
+    return n.get("labels") or {}, int(n.get("created_ns", 0))
+
+
+def _status(n: dict):
+    """What esc_nodes_update may change: cordon, escalator-taint presence, allocatable."""
+    return (bool(n.get("unschedulable")), TO_BE_REMOVED_KEY in (n.get("taints") or []),
+            n.get("cpu") or 0, n.get("mem") or 0)
+
+
+class EventQueue:
+    def __init__(self, spare: float = 0.5):
+        self.spare = float(spare)
+        self.pods: dict[str, dict] = {}            # the object store: key -> pod, name -> node
+        self.nodes: dict[str, dict] = {}           # (insertion order = arrival order)
+        self._dev_pods: dict[str, dict] = {}       # the records the device holds, as last flushed
+        self._dev_nodes: dict[str, dict] = {}
+        self._node_idx: dict[str, int] = {}
+        self._idx_node: dict[int, str] = {}
+        self._pod_id: dict[str, int] = {}
+        self._free: list[int] = []                 # heap of freed pod ids
+        self._next_id = 0
+        self._by_node: dict[str, set] = {}         # node name -> keys of pods whose node_name is it
+        self._dirty_pods: dict[str, bool] = {}     # key -> deleted since the last flush (re-add = fresh)
+        self._dirty_nodes: dict[str, bool] = {}
+        self._loaded = False
+        self.reloads = 0
+        self.reload_causes: list[str] = []         # "first", or the call that answered ESC_E_LIMIT
+        self.flushes = 0
+        self.applied = {k: 0 for k in KINDS}
+        self.touched_nodes = False                 # the last flush added nodes or reloaded
+
+    # ------------------------------------------------------------------ ingest
+    def _index_pod(self, key, old, new):
+        for p, add in ((old, False), (new, True)):
+            name = (p or {}).get("node_name") or ""
+            if not name:
+                continue
+            s = self._by_node.setdefault(name, set())
+            (s.add if add else s.discard)(key)
+            if not s:
+                del self._by_node[name]
+
+    def pod_add(self, pod: dict):
+        key = pod_key(pod)
+        self._index_pod(key, self.pods.get(key), pod)
+        self.pods[key] = pod
+        self._dirty_pods.setdefault(key, False)
+
+    pod_update = pod_add
+
+    def pod_delete(self, pod):
+        key = pod if isinstance(pod, str) else pod_key(pod)
+        old = self.pods.pop(key, None)
+        if old is None:
+            return
+        self._index_pod(key, old, None)
+        self._dirty_pods[key] = True
+
+    def node_add(self, node: dict):
+        name = node.get("name", "")
+        self.nodes[name] = node                    # back after a delete: listed last again
+        self._dirty_nodes.setdefault(name, False)
+
+    node_update = node_add
+
+    def node_delete(self, node):
+        name = node if isinstance(node, str) else node.get("name", "")
+        if self.nodes.pop(name, None) is not None:
+            self._dirty_nodes[name] = True
+
+    # ------------------------------------------------------------------ lookups
+    def node_index(self, name: str):
+        return self._node_idx.get(name)
+
+    def node_name(self, index: int):
+        return self._idx_node.get(int(index))
+
+    def pod_id(self, key: str):
+        return self._pod_id.get(key)
+
+    def live_nodes(self) -> list[dict]:
+        """The device's nodes in snapshot-index order (the lister order)."""
+        return [self._dev_nodes[self._idx_node[j]] for j in sorted(self._idx_node)]
+
+    def live_pods(self) -> list[dict]:
+        return [self._dev_pods[k] for k in sorted(self._pod_id, key=self._pod_id.get)]
+
+    # ------------------------------------------------------------------ flush
+    def _take_id(self) -> int:
+        if self._free:
+            return heapq.heappop(self._free)
+        self._next_id += 1
+        return self._next_id - 1
+
+    def _call(self, kind: str, n: int, fn, *args):
+        try:
+            rc = fn(*args)
+        except Exception as e:
+            if getattr(e, "code", None) == ESC_E_LIMIT:
+                raise _Reload(kind) from None
+            raise
+        if kind == "pods_upsert" and rc == ESC_E_LIMIT:    # the one call that returns its code
+            raise _Reload(kind)
+        self.applied[kind] += n
+        return rc
+
+    def _target(self, pod: dict) -> int:
+        return self._node_idx.get(pod.get("node_name") or "", NONE) if pod.get("node_name") else NONE
+
+    def flush(self, ctx):
+        """Applies what was ingested since the last flush: at most one call per kind, node
+        calls first (pods bind to nodes), or one reload."""
+        self.flushes += 1
+        self.touched_nodes = False
+        dirty_p, dirty_n = self._dirty_pods, self._dirty_nodes
+        self._dirty_pods, self._dirty_nodes = {}, {}
+        if not self._loaded:
+            ctx.set_spare(self.spare)
+            self.reload_causes.append("first")
+            return self._reload(ctx, dirty_p, dirty_n)
+        try:
+            self._apply(ctx, dirty_p, dirty_n)
+        except _Reload as e:
+            self.reload_causes.append(str(e))
+            self._reload(ctx, dirty_p, dirty_n)
+
+    def _apply(self, ctx, dirty_p, dirty_n):
+        dev_n, idx = self._dev_nodes, self._node_idx
+        # --- nodes: delete, add, then the three kinds of update
+        gone = [m for m, fresh in dirty_n.items() if m in dev_n and (fresh or m not in self.nodes)]
+        if gone:
+            self._call("nodes_delete", len(gone), ctx.nodes_delete, np.array([idx[m] for m in gone], np.int64))
+            for m in gone:
+                del self._idx_node[idx.pop(m)]
+                del dev_n[m]
+        new = [m for m in self.nodes if m in dirty_n and m not in dev_n]
+        if new:
+            _, packed = ctx.pack([], [self.nodes[m] for m in new])
+            ids = self._call("nodes_add", len(new), ctx.nodes_add, packed)
+            for m, j in zip(new, ids):
+                idx[m] = int(j)
+                self._idx_node[int(j)] = m
+                dev_n[m] = self.nodes[m]
+            self.touched_nodes = True
+        fresh_nodes = set(new)
+        relabel, update, facts = [], [], list(new)
+        for m in dirty_n:
+            if m in fresh_nodes or m not in self.nodes:
+                continue
+            old, cur = dev_n[m], self.nodes[m]
+            if _shape(old) != _shape(cur):
+                relabel.append(m)
+            elif _status(old) != _status(cur):
+                update.append(m)
+            if _facts(old) != _facts(cur):
+                facts.append(m)
+        if relabel:
+            _, packed = ctx.pack([], [self.nodes[m] for m in relabel])
+            self._call("nodes_relabel", len(relabel), ctx.nodes_relabel, np.array([idx[m] for m in relabel], np.int64),
+                       packed)
+        if update:
+            _, packed = ctx.pack([], [self.nodes[m] for m in update])
+            self._call("nodes_update", len(update), ctx.nodes_update, np.array([idx[m] for m in update], np.int64),
+                       packed["flags"], packed["cpu"], packed["mem"])
+        if facts:
+            f = [_facts(self.nodes[m]) for m in facts]
+            self._call("nodes_facts", len(facts), ctx.nodes_facts, np.array([idx[m] for m in facts], np.int64),
+                       np.array([t for t, _ in f], np.int64), np.array([d for _, d in f], np.uint8))
+        for m in dirty_n:
+            if m in self.nodes:
+                dev_n[m] = self.nodes[m]
+        # --- pods: delete, upsert, bind
+        dev_p, pid = self._dev_pods, self._pod_id
+        gone = [k for k, fresh in dirty_p.items() if k in dev_p and (fresh or k not in self.pods)]
+        if gone:
+            self._call("pods_delete", len(gone), ctx.pods_delete, np.array([pid[k] for k in gone], np.int64))
+            for k in gone:
+                heapq.heappush(self._free, pid.pop(k))
+                del dev_p[k]
+        born = [k for k in self.pods if k in dirty_p and k not in dev_p]
+        changed = [k for k in dirty_p if k in dev_p and k in self.pods]
+        upsert = born + [k for k in changed if _pod_spec(dev_p[k]) != _pod_spec(self.pods[k])]
+        for k in born:
+            pid[k] = self._take_id()
+        if upsert:
+            packed, _ = ctx.pack([self.pods[k] for k in upsert], [])
+            self._call("pods_upsert", len(upsert), ctx.pods_upsert, np.array([pid[k] for k in upsert], np.int64),
+                       packed)
+        bind = list(born)
+        seen = set(born)
+        for k in changed:
+            if (dev_p[k].get("node_name") or "") != (self.pods[k].get("node_name") or ""):
+                bind.append(k)
+                seen.add(k)
+        for m in new:                                      # pods that named the node before it came
+            for k in sorted(self._by_node.get(m, ()), key=lambda k: pid.get(k, -1)):
+                if k not in seen and k in pid:
+                    bind.append(k)
+                    seen.add(k)
+        for k in dirty_p:
+            if k in self.pods:
+                dev_p[k] = self.pods[k]
+        if bind:
+            self._call("pods_bind", len(bind), ctx.pods_bind, np.array([pid[k] for k in bind], np.int64),
+                       np.array([self._target(self.pods[k]) for k in bind], np.uint32))
+
+    def _reload(self, ctx, dirty_p, dirty_n):
+        """One full load from the object store: the nodes the device held keep their order
+        (compacted in snapshot-index order, so allNodes[0] and the tie order stay), nodes it
+        never held follow in arrival order — a node deleted and added again under its name
+        since the device saw it among them; pods are renumbered the same way."""
+        order_n = [m for m in sorted(self._node_idx, key=self._node_idx.get)
+                   if m in self.nodes and not dirty_n.get(m)]
+        keep = set(order_n)
+        order_n += [m for m in self.nodes if m not in keep]
+        had = [k for k in sorted(self._pod_id, key=self._pod_id.get) if k in self.pods and not dirty_p.get(k)]
+        keep = set(had)
+        order_p = had + [k for k in self.pods if k not in keep]
+        nodes = [self.nodes[m] for m in order_n]
+        pods = [self.pods[k] for k in order_p]
+        P, N = ctx.pack(pods, nodes)
+        ctx.load(P, N)
+        ctx.load_placement(*placement(pods, nodes))
+        self._node_idx = {m: j for j, m in enumerate(order_n)}
+        self._idx_node = dict(enumerate(order_n))
+        self._pod_id = {k: i for i, k in enumerate(order_p)}
+        self._free, self._next_id = [], len(order_p)
+        self._dev_nodes = dict(zip(order_n, nodes))
+        self._dev_pods = dict(zip(order_p, pods))
+        self._loaded = True
+        self.touched_nodes = True
+        self.reloads += 1

@@ -513,7 +513,7 @@ int32_t esc_nodes_update(esc_ctx* ctx, const int64_t* ids, int64_t n, const uint
  * member) and its dry-mode tracker entries are dropped (a host that re-adds a tracked
  * name re-applies it with esc_tracker_update).  Both keep esc_load_placement's binding
  * (an added node starts with no pods, no taint time and no no-delete flag until
- * esc_pods_bind / a node-facts refresh); an add that does not fit returns ESC_E_LIMIT
+ * esc_pods_bind / esc_nodes_facts); an add that does not fit returns ESC_E_LIMIT
  * with nothing applied (reload).  Every check
  * depends on the node table alone, which every rank holds, so all ranks of a sharded job
  * accept or refuse the same batch. */
@@ -562,9 +562,10 @@ int32_t esc_tracker_list(const esc_ctx* ctx, int32_t group, int64_t* idx_out, in
  * esc_pods_delete drops it, esc_pods_bind moves pods between nodes (runs per node keep
  * esc_set_spare room; ESC_E_LIMIT when a run is full).  Node additions / deletions keep
  * it: every node-table slot (esc_set_spare's free slots included) has a run and facts, a
- * free slot's run sized for the mean pods per node plus the spare fraction; refresh the
- * facts (esc_load_placement with pod_node NULL, n_nodes entries: the table as it is now,
- * deleted slots included) when taints change.  esc_try_remove then evaluates, per
+ * free slot's run sized for the mean pods per node plus the spare fraction; when taints
+ * change, patch the facts of those nodes (esc_nodes_facts) or refresh the whole table's
+ * (esc_load_placement with pod_node NULL, n_nodes entries: the table as it is now,
+ * deleted slots included).  esc_try_remove then evaluates, per
  * group, its tainted nodes in snapshot order: now - taintTime > soft grace and (NodeEmpty
  * or > hard grace) -> delete (never in dry mode).
  * Several ranks (each holding its pod shard): the per-node occupancy is this rank's pods
@@ -580,6 +581,19 @@ typedef struct esc_removal {
 } esc_removal;
 int32_t esc_load_placement(esc_ctx* ctx, const uint32_t* pod_node, const int64_t* taint_unix_s,
                            const uint8_t* no_delete);
+/* The per-node facts of table slots ids[0..n) in place (a node Update that sets or clears
+ * the escalator taint's time or the no-delete annotation, or a node esc_nodes_add just
+ * appended): values as esc_load_placement's (INT64_MIN = no taint time, non-zero no_delete =
+ * safe from deletion).  Pod bindings and occupancy stay.  The batch is staged once and
+ * scattered by one launch; the call completes before returning and a previous
+ * esc_try_remove result is no longer current.  All or nothing: ESC_E_STATE when no
+ * placement is loaded, ESC_E_INVAL for a null argument with n > 0, an id outside the
+ * table, an ESC_NF_ABSENT slot or a repeated id (nothing applied); n == 0 is ESC_OK.  A
+ * device failure after the first write marks the node side stale, like esc_nodes_update.
+ * A multi-device context applies the batch on every device; every rank of a sharded job
+ * makes the call (each holds the whole node table). */
+int32_t esc_nodes_facts(esc_ctx* ctx, const int64_t* ids, int64_t n, const int64_t* taint_unix_s,
+                        const uint8_t* no_delete);
 int32_t esc_try_remove(esc_ctx* ctx, int64_t now_unix_ns, const int64_t* soft_grace_ns,
                        const int64_t* hard_grace_ns, esc_removal* out);
 int32_t esc_pods_bind(esc_ctx* ctx, const int64_t* ids, const uint32_t* pod_node, int64_t n);
