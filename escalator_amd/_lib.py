@@ -74,6 +74,14 @@ class Removal(C.Structure):
     _fields_ = [("n_candidates", i64), ("n_delete", i64), ("pods_remaining", i64), ("reserved", i64)]
 
 
+ESC_NN_BUCKETS, ESC_NN_LAG_OVERFLOW = 30, 1
+
+
+class NewNodes(C.Structure):
+    _fields_ = [("n_new", i64), ("n_observed", i64), ("lag_sum_ns", i64), ("flags", i64),
+                ("bucket", u32 * ESC_NN_BUCKETS)]
+
+
 class KV(C.Structure):
     _fields_ = [("key", cstr), ("value", cstr)]
 
@@ -183,6 +191,9 @@ _SIGS = {
     "esc_reap_upload": (i32, [VP, P(u32)]),
     "esc_reap_finish": (i32, [VP, i64, P(i64), P(i64), P(Removal)]),
     "esc_removal_nodes": (i32, [VP, i32, P(i64), i64, P(i64)]),
+    "esc_nodes_instantiated": (i32, [VP, P(i64), i64, P(i64)]),
+    "esc_new_nodes_eval": (i32, [VP, P(i64), P(NewNodes)]),
+    "esc_new_nodes_list": (i32, [VP, i32, P(i64), P(C.c_uint8), i64, P(i64)]),
     "esc_set_metrics": (i32, [VP, i32]),
     "esc_metrics_results": (i32, [VP, P(GroupMetrics)]),
     "esc_use_graph": (i32, [VP, i32]),

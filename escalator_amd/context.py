@@ -21,6 +21,9 @@ REMOVAL_DTYPE = np.dtype([(n, np.int64) for n, _ in L.Removal._fields_])
 DECISION_DTYPE = np.dtype({"names": [n for n, _ in L.GroupDecision._fields_],
                            "formats": [np.float64, np.float64, np.int64, np.int64, np.int64, np.int64,
                                        np.int32, np.int32, np.int32, np.int32]})
+NEW_NODES_DTYPE = np.dtype([("n_new", np.int64), ("n_observed", np.int64), ("lag_sum_ns", np.int64),
+                            ("flags", np.int64), ("bucket", np.uint32, (L.ESC_NN_BUCKETS,))])
+assert NEW_NODES_DTYPE.itemsize == C.sizeof(L.NewNodes) == 152
 assert TOTALS_DTYPE.itemsize == C.sizeof(L.GroupTotals)
 assert DECISION_DTYPE.itemsize == C.sizeof(L.GroupDecision)
 assert METRICS_DTYPE.itemsize == C.sizeof(L.GroupMetrics)
@@ -557,6 +560,41 @@ class Context:
         L.check(self.lib.esc_removal_nodes(self.handle, group, out.ctypes.data_as(C.POINTER(C.c_int64)), len(out),
                                            C.byref(n)), "esc_removal_nodes")
         return out[:n.value]
+
+    # ------------------------------ newly registered nodes (controller.go:157-189)
+    def nodes_instantiated(self, ids, inst_ns):
+        """The cloud instances' instantiation times (Unix ns, INT64_MIN = unknown) of the
+        nodes `ids`, in place (esc_nodes_instantiated)."""
+        ids = np.ascontiguousarray(ids, np.int64)
+        t = np.ascontiguousarray(inst_ns, np.int64)
+        if len(ids) != len(t):
+            raise ValueError("nodes_instantiated: ids and inst_ns differ in length")
+        L.check(self.lib.esc_nodes_instantiated(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids),
+                                                t.ctypes.data_as(C.POINTER(C.c_int64))), "esc_nodes_instantiated")
+
+    def new_nodes(self, since_ns) -> np.ndarray:
+        """calculateNewNodeMetrics for every group: since_ns[g] = the group's lastScaleOut
+        (Unix ns; INT64_MIN = the zero time, INT64_MAX = not evaluated).  Returns the
+        per-group records (n_new, n_observed, lag_sum_ns, flags, bucket[30])."""
+        s_ = np.ascontiguousarray(np.broadcast_to(np.asarray(since_ns, np.int64), (self.G,)))
+        out = np.zeros(self.G, NEW_NODES_DTYPE)
+        L.check(self.lib.esc_new_nodes_eval(self.handle, s_.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            out.ctypes.data_as(C.POINTER(L.NewNodes))), "esc_new_nodes_eval")
+        return out
+
+    def new_nodes_list(self, group: int) -> tuple[np.ndarray, np.ndarray]:
+        """(snapshot indices ascending, known bytes) of the nodes the last new_nodes found
+        new for `group`; known[i] == 0: the host has to look the instance up."""
+        n = C.c_int64()
+        rc = self.lib.esc_new_nodes_list(self.handle, group, None, None, 0, C.byref(n))
+        if rc not in (0, L.ESC_E_LIMIT):
+            L.check(rc, "esc_new_nodes_list")
+        idx = np.zeros(max(n.value, 1), np.int64)
+        known = np.zeros(max(n.value, 1), np.uint8)
+        L.check(self.lib.esc_new_nodes_list(self.handle, group, idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            known.ctypes.data_as(C.POINTER(C.c_uint8)), len(idx), C.byref(n)),
+                "esc_new_nodes_list")
+        return idx[:n.value], known[:n.value]
 
     # ------------------------------------------------------------- ordering
     def sort_nodes(self):

@@ -70,6 +70,27 @@ def untaint_newest_n(created_ns, n: int, device: int = 0) -> list[int]:
 ACTUATOR_METHODS = ("taint", "untaint", "target_size", "max_size", "increase_size", "delete_nodes")
 
 
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+# the decision branches after which scaleNodeGroup reaches calculateNewNodeMetrics
+# (controller.go:325): past every early return and the lock
+ARMED_BRANCHES = ("fast_down", "slow_down", "scale_up", "none")
+
+
+def new_node_since(prev_delta: int, branch: str, status: int, last_scale_out) -> int:
+    """The `since` word of one group for esc_new_nodes_eval (Context.new_nodes).
+
+    calculateNewNodeMetrics (controller.go:157-189) runs when this scan's scaleNodeGroup gets
+    to :325 — its branch is one of ARMED_BRANCHES; empty, gate, below_min, pct_err and locked
+    return before — and does its loop only when the previous scan's delta was positive
+    (``nodeGroup.scaleDelta > 0``, :165).  `status` takes no part: a scale_up whose
+    calcScaleUpDelta fails (ESC_ST_ERR_NEG_DELTA) fails at :346, after :325.  Armed: the
+    group's lastScaleOut in Unix ns, INT64_MIN for ``None`` (the zero time.Time: every node is
+    newer); unarmed: INT64_MAX (not evaluated)."""
+    if int(prev_delta) > 0 and branch in ARMED_BRANCHES:
+        return INT64_MIN if last_scale_out is None else int(last_scale_out)
+    return INT64_MAX
+
+
 class SimulatedCloud:
     """The actuator used when none is given: every Kubernetes write succeeds, and the
     cloud node group behaves like the reference tests' mock (pkg/test/cloud_provider.go):
@@ -131,7 +152,19 @@ class Controller:
     when failed writes use up the slack (``walk_fallback`` in the group's result).  The ``actuator`` provides
     ``taint(g, node) -> bool``, ``untaint(g, node) -> bool``, ``target_size(g)``,
     ``max_size(g)``, ``increase_size(g, n)`` and ``delete_nodes(g, nodes)`` (raising on an
-    API error); without one a ``SimulatedCloud`` stands in (every write succeeds)."""
+    API error); without one a ``SimulatedCloud`` stands in (every write succeeds).
+
+    ``scale_delta[g]`` and ``last_scale_out[g]`` are NodeGroupState's remaining two fields
+    (controller.go:38-39): the delta each scan returned, error returns included (:434), and
+    ``clock()`` of the scan's ``delta > 0`` arm (:376; ``None`` = the zero time).  They feed
+    calculateNewNodeMetrics (controller.go:157-189), which is opt-in: when the actuator has
+    ``instantiation_time(g, node) -> int | None`` (Unix ns; ``None`` or raising is GetInstance's
+    error, :174), every scan evaluates the armed groups (``new_node_since``) on the device,
+    asks the actuator about the nodes listed as unknown, uploads the answers, evaluates again
+    if any came, and adds ``r["new_nodes"]`` (n_new, n_observed, n_unknown, lag_sum_ns, buckets,
+    expected = the previous delta: the reference warns when it differs from n_observed, :185)
+    to the armed groups' records — before the action switch, as the reference does.  Without
+    that method nothing is called and no key is added."""
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
                  selection_slack: int = 4):
@@ -145,6 +178,12 @@ class Controller:
         self.state = [{"locked": False, "requested_nodes": 0, "cached_cpu_m": 0, "cached_mem_b": 0}
                       for _ in groups]
         self.lock_time = [None] * len(groups)          # scaleLock.lockTime (None: never locked)
+        self.scale_delta = [0] * len(groups)           # NodeGroupState.scaleDelta   controller.go:38, :434
+        self.last_scale_out = [None] * len(groups)     # NodeGroupState.lastScaleOut controller.go:39, :376
+        self.inst_ns: dict[str, int] = {}              # node name -> instantiation time (Unix ns) learned so far
+        self._inst_created: dict[str, int] = {}        # ... and the creation time of the node it was learned for
+        self._created: list[int] = []                  # creation times of this scan's listing
+        self._new_nodes = None
         self.taint_tracker = {g: [] for g in range(len(groups))}
         self.clock = clock or time.time_ns
         self.actuator = actuator if actuator is not None else SimulatedCloud(self.groups)
@@ -249,15 +288,62 @@ class Controller:
             except Exception as e:
                 out["reap_err"] = str(e)
 
+    def _learned(self, name: str, j: int, t: int):
+        """Keeps an answer in the host's copy of the device's per-node fact: name -> time, and
+        beside it the creation time of the node that got the answer (this scan's listing)."""
+        self.inst_ns[name] = t
+        self._inst_created[name] = self._created[j]
+
+    def _new_node_pass(self, dec, names):
+        """calculateNewNodeMetrics (controller.go:157-189) for the groups this decision arms:
+        {g: record}, or None when the actuator has no ``instantiation_time``."""
+        lookup = getattr(self.actuator, "instantiation_time", None)
+        if not callable(lookup):
+            return None
+        since = [new_node_since(self.scale_delta[g], L.BRANCHES[int(dec[g]["branch"])], int(dec[g]["status"]),
+                                self.last_scale_out[g]) for g in range(len(self.groups))]
+        armed = [g for g, s in enumerate(since) if s != INT64_MAX]
+        if not armed:
+            return {}
+        rec = self.ctx.new_nodes(since)
+        asked, ids, times = set(), [], []
+        for g in armed:
+            if int(rec[g]["n_new"]) == int(rec[g]["n_observed"]):
+                continue
+            idx, known = self.ctx.new_nodes_list(g)
+            for j in (int(j) for j in idx[known == 0]):
+                if j in asked:                             # (a node of two groups: asked once)
+                    continue
+                asked.add(j)
+                try:                                       # GetInstance, controller.go:173
+                    t = lookup(g, j)
+                except Exception:
+                    t = None
+                if t is not None:                          # an instance's launch time never changes
+                    ids.append(j)
+                    times.append(int(t))
+                    self._learned(names[j], j, int(t))
+        if ids:
+            self.ctx.nodes_instantiated(ids, times)
+            rec = self.ctx.new_nodes(since)
+        return {g: {"n_new": int(rec[g]["n_new"]), "n_observed": int(rec[g]["n_observed"]),
+                    "n_unknown": int(rec[g]["n_new"]) - int(rec[g]["n_observed"]),
+                    "lag_sum_ns": int(rec[g]["lag_sum_ns"]), "buckets": [int(x) for x in rec[g]["bucket"]],
+                    "expected": int(self.scale_delta[g])} for g in armed}
+
+    def _list_error(self, e) -> list[dict]:
+        self.scale_delta = [0] * len(self.groups)          # scaleNodeGroup returned 0, err (controller.go:434)
+        return [{"delta": 0, "err": str(e)} for _ in self.groups]
+
     def run_once(self, list_pods, list_nodes) -> list[dict]:
         try:
             pods = list_pods()
         except Exception as e:                   # controller.go:195-198
-            return [{"delta": 0, "err": str(e)} for _ in self.groups]
+            return self._list_error(e)
         try:
             nodes = list_nodes()
         except Exception as e:                   # controller.go:202-205
-            return [{"delta": 0, "err": str(e)} for _ in self.groups]
+            return self._list_error(e)
         from .objects import placement
         now = self.clock()
         self._lock_states(now)
@@ -277,7 +363,21 @@ class Controller:
         soft = [int(grp.get("soft_delete_grace_ns", 0)) for grp in self.groups]
         hard = [int(grp.get("hard_delete_grace_ns", 0)) for grp in self.groups]
         self._removal = self.ctx.try_remove(now, soft, hard)
-        return self._act(tot, dec, [n.get("name", "") for n in nodes])
+        names = [n.get("name", "") for n in nodes]
+        if callable(getattr(self.actuator, "instantiation_time", None)):
+            # the load left every instantiation time unknown: the ones learned on earlier scans
+            # go back in.  A name that is no longer listed is forgotten, and so is one whose
+            # node was registered again between two scans (its creation time differs): a node
+            # back under a name is a new instance
+            index = {m: j for j, m in enumerate(names)}
+            self._created = [int(n.get("created_ns", 0)) for n in nodes]
+            self.inst_ns = {m: t for m, t in self.inst_ns.items()
+                            if m in index and self._inst_created.get(m) == self._created[index[m]]}
+            self._inst_created = {m: self._inst_created[m] for m in self.inst_ns}
+            if self.inst_ns:
+                self.ctx.nodes_instantiated([index[m] for m in self.inst_ns], list(self.inst_ns.values()))
+        self._new_nodes = self._new_node_pass(dec, names)
+        return self._act(tot, dec, names)
 
     def _act(self, tot, dec, names) -> list[dict]:
         """The per-group action switch of one scan (controller.go:265-383) over the decision
@@ -296,6 +396,8 @@ class Controller:
                  "totals": {k: int(tot[g][k]) for k in tot.dtype.names},
                  "tainted_now": [], "untainted_now": [], "added": 0, "removed": [], "pods_evicted": 0,
                  "walk_fallback": False}
+            if self._new_nodes and g in self._new_nodes:                  # controller.go:325
+                r["new_nodes"] = self._new_nodes[g]
             n_tainted, n_untainted = int(tot["n_tainted"][g]), int(tot["n_untainted"][g])
             if branch == "below_min":                                     # controller.go:281-295
                 r["delta"], r["err"] = self._scale_up(g, r["delta"], n_tainted, names, r)
@@ -310,8 +412,10 @@ class Controller:
                         r["action_err"] = "taint clamp"                   # scale_down.go:150-154
                 elif r["delta"] > 0:
                     _, r["action_err"] = self._scale_up(g, r["delta"], n_tainted, names, r)   # :372-375
+                    self.last_scale_out[g] = self.clock()                 # controller.go:376
                 else:
                     self._reap(g, r)                                      # default: controller.go:377-383
+            self.scale_delta[g] = int(r["delta"])                         # state.scaleDelta = delta, controller.go:434
             out.append(r)
         return out
 
@@ -359,6 +463,11 @@ class ResidentController(Controller):
         self.spare = float(spare)
         self.events = EventQueue(spare=self.spare)
 
+    def _learned(self, name: str, j: int, t: int):
+        """The queue keeps the cache: it drops a name on node_delete and re-sends the cache
+        after a reload (the only thing that loses the device's copy)."""
+        self.events.inst_ns[name] = t
+
     def _sync_trackers(self):
         """filterNodes reads the tracker by name (controller.go:126-138): every tracked name
         with a live node is tracked on the device."""
@@ -387,7 +496,9 @@ class ResidentController(Controller):
         soft = [int(grp.get("soft_delete_grace_ns", 0)) for grp in self.groups]
         hard = [int(grp.get("hard_delete_grace_ns", 0)) for grp in self.groups]
         self._removal = self.ctx.try_remove(now, soft, hard)
-        out = self._act(tot, dec, _NodeNames(self.events))
+        names = _NodeNames(self.events)
+        self._new_nodes = self._new_node_pass(dec, names)
+        out = self._act(tot, dec, names)
         for g, r in enumerate(out):                      # the dry-mode walks' tracker changes
             if self.groups[g]["dry_mode"] and (r.get("tainted_now") or r.get("untainted_now")):
                 self.ctx.tracker_update(g, add=r.get("tainted_now", []), remove=r.get("untainted_now", []))

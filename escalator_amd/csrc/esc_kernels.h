@@ -555,6 +555,23 @@ hipError_t launch_patch(const PatchTargets& t, const uint64_t* where, const uint
 hipError_t launch_node_facts(int64_t* taint_s, uint8_t* no_delete, const int64_t* ids, const int64_t* ev_taint,
                              const uint8_t* ev_nd, int64_t n, hipStream_t st);
 
+// calculateNewNodeMetrics (controller.go:157-189) for every group: k_new_nodes, one wave per
+// group over its pair's entries (K7's walk).  A list word is the node's snapshot index, with
+// NN_UNKNOWN set when its instantiation time is unknown (node indices are < 2^28, MEMB_NODE_MASK).
+constexpr uint32_t NN_UNKNOWN = 1u << 31;
+constexpr int64_t NN_BUCKET_NS = 60ll * 1000000000ll;   // metrics.go:190: bounds 60, 120, ..., 1740 s
+struct NewNodesDev {
+    const int64_t* inst_ns;    // [node-table capacity] instantiation time, Unix ns (INT64_MIN: unknown)
+    const int64_t* since;      // [G] lastScaleOut (INT64_MIN: zero time; INT64_MAX: group not evaluated)
+    const uint32_t* list_off;  // [G] offset of each group's new-node list (its pair's entry capacity)
+    uint32_t* list;
+    esc_new_nodes* out;        // [G]
+};
+hipError_t launch_new_nodes(const NodeDev& n, const GroupDev& g, const NewNodesDev& w, hipStream_t st);
+// esc_nodes_instantiated / esc_nodes_delete: inst_ns[ids[i]] = ev_inst[i], or INT64_MIN for
+// every listed id when ev_inst is null; one event per thread (ids unique).
+hipError_t launch_node_inst(int64_t* inst_ns, const int64_t* ids, const int64_t* ev_inst, int64_t n, hipStream_t st);
+
 
 // Ordering (K5), see esc_kernels.hip: the age index (once per snapshot) and the per-decision
 // (group, class) partition.

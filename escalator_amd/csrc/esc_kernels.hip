@@ -3045,9 +3045,15 @@ __device__ __forceinline__ bool podref_has(const PodRef& r, const uint32_t* xp, 
 }
 
 // Go's time.Time.Sub saturates at the int64 Duration range.
-__device__ __forceinline__ int64_t go_sub_ns(int64_t now_ns, int64_t t_s) {
-    const __int128 d = (__int128)now_ns - (__int128)t_s * 1000000000;
+__device__ __forceinline__ int64_t go_sat_ns(__int128 d) {
     return d > (__int128)INT64_MAX ? INT64_MAX : (d < (__int128)INT64_MIN ? INT64_MIN : (int64_t)d);
+}
+__device__ __forceinline__ int64_t go_sub_ns(int64_t now_ns, int64_t t_s) {
+    return go_sat_ns((__int128)now_ns - (__int128)t_s * 1000000000);
+}
+// the same with both times in ns
+__device__ __forceinline__ int64_t go_sub_ns_ns(int64_t t_ns, int64_t u_ns) {
+    return go_sat_ns((__int128)t_ns - (__int128)u_ns);
 }
 }  // namespace
 
@@ -3174,6 +3180,84 @@ __global__ __launch_bounds__(64) void k_try_remove(NodeDev N, GroupDev G, Remova
     if (lane == 0) R.out[g] = RmRec{cand, del, pods};
 }
 
+// The instantiation-time fact in place (esc_nodes_instantiated; esc_nodes_delete resets the
+// slots with ev_inst null).  The host refuses a repeated id: every element has one writer.
+__global__ __launch_bounds__(256) void k_node_inst(int64_t* __restrict__ inst_ns, const int64_t* __restrict__ ids,
+                                                   const int64_t* __restrict__ ev_inst, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    inst_ns[ids[i]] = ev_inst ? ev_inst[i] : INT64_MIN;
+}
+
+// calculateNewNodeMetrics (controller.go:157-189) for every group: K7's walk — one wave per
+// group over its pair's entries, the next 64 entries' e_flags / e_node loads in flight while
+// this chunk gathers created[j] — over every live entry (NodeInfoMap holds allNodes,
+// controller.go:259: untainted, tainted and cordoned alike).  inst_ns[j] is gathered only by
+// the lanes whose node is new (created > since, :171).  The new nodes are listed compacted by
+// ballot and prefix popcount (as K7's rm_list; NN_UNKNOWN marks those the host has to ask the
+// cloud provider about), the lags are counted into the histogram's buckets in LDS and summed
+// split lo32 / hi so the total cannot wrap unnoticed.  No global atomics: the record, written
+// once by lane 0, and the list are deterministic.
+__global__ __launch_bounds__(64) void k_new_nodes(NodeDev N, GroupDev G, NewNodesDev W) {
+    __shared__ uint32_t bk[ESC_NN_BUCKETS];
+    const int32_t g = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t since = W.since[g];
+    if (lane < ESC_NN_BUCKETS) bk[lane] = 0;
+    __syncthreads();
+    uint32_t n_new = 0, n_obs = 0;
+    unsigned long long lo = 0, hi = 0;                         // lag = (int32)hi << 32 | lo, summed apart
+    if (since != INT64_MAX) {                                  // (uniform: the group is evaluated this scan)
+        const uint32_t q = G.gpair[g];
+        const int64_t e0 = N.piece_off[N.pp_off[q]], e1 = N.piece_off[N.pp_off[q + 1]];
+        const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+        uint32_t* __restrict__ list = W.list + W.list_off[g];
+        uint32_t f = ESC_NF_ABSENT, j = 0;
+        if (e0 + lane < e1) { f = N.e_flags[e0 + lane]; j = N.e_node[e0 + lane]; }
+        for (int64_t b = e0; b < e1; b += 64) {
+            const int64_t en = b + 64 + lane;
+            uint32_t nf = ESC_NF_ABSENT, nj = 0;
+            if (en < e1) { nf = N.e_flags[en]; nj = N.e_node[en]; }
+            int64_t cr = 0;
+            bool nw = false, known = false;
+            if (!(f & ESC_NF_ABSENT)) {                        // (a spare or retired entry has no node)
+                cr = N.created[j];
+                nw = cr > since;
+            }
+            if (nw) {
+                const int64_t inst = W.inst_ns[j];
+                known = inst != INT64_MIN;
+                if (known) {
+                    const int64_t lag = go_sub_ns_ns(cr, inst);   // Time.Sub: saturating
+                    // the first bound >= lag: bounds 60 s * (k + 1), k < 29; above them +Inf
+                    const int64_t k = lag <= 0 ? 0 : (lag - 1) / NN_BUCKET_NS;
+                    atomicAdd(&bk[k < ESC_NN_BUCKETS - 1 ? k : ESC_NN_BUCKETS - 1], 1u);
+                    lo += (unsigned long long)(uint32_t)lag;
+                    hi += (unsigned long long)(lag >> 32);     // arithmetic: two's complement sum
+                }
+            }
+            const unsigned long long mn = __ballot(nw);
+            if (nw) list[n_new + __popcll(mn & lt)] = j | (known ? 0u : NN_UNKNOWN);
+            n_new += (uint32_t)__popcll(mn);
+            n_obs += (uint32_t)__popcll(__ballot(known));
+            f = nf; j = nj;
+        }
+        lo = wave_total64(lo);
+        hi = wave_total64(hi);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        esc_new_nodes r;
+        const __int128 total = (__int128)(int64_t)hi * ((__int128)1 << 32) + (__int128)lo;
+        r.n_new = n_new;
+        r.n_observed = n_obs;
+        r.lag_sum_ns = (int64_t)(unsigned long long)total;
+        r.flags = (total > (__int128)INT64_MAX || total < (__int128)INT64_MIN) ? ESC_NN_LAG_OVERFLOW : 0;
+        for (int k = 0; k < ESC_NN_BUCKETS; ++k) r.bucket[k] = bk[k];
+        W.out[g] = r;
+    }
+}
+
 // ===================================================================== launchers
 hipError_t launch_pod_bigtiles(const PodDev& p, const GroupDev& g, const uint32_t* tiles, int64_t n_big,
                                int64_t* wide, hipStream_t st) {
@@ -3279,6 +3363,18 @@ hipError_t launch_node_facts(int64_t* taint_s, uint8_t* no_delete, const int64_t
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_node_facts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, taint_s, no_delete, ids,
                        ev_taint, ev_nd, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_new_nodes(const NodeDev& n, const GroupDev& g, const NewNodesDev& w, hipStream_t st) {
+    if (g.G <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_new_nodes, dim3(g.G), dim3(64), 0, st, n, g, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_node_inst(int64_t* inst_ns, const int64_t* ids, const int64_t* ev_inst, int64_t n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_node_inst, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, inst_ns, ids, ev_inst, n);
     return hipGetLastError();
 }
 

@@ -64,6 +64,9 @@ int32_t multi_pods_bind(esc_ctx* c, const int64_t* ids, const uint32_t* pod_node
 int32_t multi_nodes_update(esc_ctx* c, const int64_t* ids, int64_t n, const uint32_t* flags, const int64_t* cpu,
                            const int64_t* mem);
 int32_t multi_nodes_facts(esc_ctx* c, const int64_t* ids, int64_t n, const int64_t* taint_s, const uint8_t* no_delete);
+int32_t multi_nodes_instantiated(esc_ctx* c, const int64_t* ids, int64_t n, const int64_t* inst_ns);
+int32_t multi_new_nodes_eval(esc_ctx* c, const int64_t* since_ns, esc_new_nodes* out);
+int32_t multi_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known, int64_t cap, int64_t* n_out);
 int32_t multi_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out);
 int32_t multi_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s);

@@ -456,6 +456,22 @@ int32_t multi_nodes_facts(esc_ctx* c, const int64_t* ids, int64_t n, const int64
     return node_event(c, [&](int i) { return esc_nodes_facts(M(c).subs[i], ids, n, taint_s, no_delete); });
 }
 
+int32_t multi_nodes_instantiated(esc_ctx* c, const int64_t* ids, int64_t n, const int64_t* inst_ns) {
+    return node_event(c, [&](int i) { return esc_nodes_instantiated(M(c).subs[i], ids, n, inst_ns); });
+}
+
+// Every device holds the whole node table and its instantiation times: one of them answers
+// every group (no exchange).
+int32_t multi_new_nodes_eval(esc_ctx* c, const int64_t* since_ns, esc_new_nodes* out) {
+    if (M(c).diverged) return ESC_E_STATE;
+    return esc_new_nodes_eval(M(c).subs[0], since_ns, out);
+}
+
+int32_t multi_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known, int64_t cap, int64_t* n_out) {
+    if (M(c).diverged) return ESC_E_STATE;
+    return esc_new_nodes_list(M(c).subs[0], g, idx, known, cap, n_out);
+}
+
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s) {
     if (M(c).diverged) return ESC_E_STATE;
     if (int32_t rc = nodes_relabel_check(M(c).subs[0], ids, s)) return rc;   // nothing applied anywhere

@@ -379,6 +379,14 @@ struct esc_ctx {
     std::vector<int64_t> h_soft, h_hard;                      // grace periods last uploaded
     bool rm_valid = false;                                    // esc_try_remove results current
     int64_t rm_nodes = -1;                                    // node count the reaping buffers are sized for
+    // newly registered nodes (calculateNewNodeMetrics, controller.go:157-189): the per-node
+    // instantiation time belongs to the node table (esc_load_nodes: every slot unknown)
+    int64_t *d_inst = nullptr, *d_nn_since = nullptr;         // [n_cap], [G]
+    uint32_t *d_nn_off = nullptr, *d_nn_list = nullptr;       // list offsets per group (as h_rm_off), the lists
+    esc_new_nodes* d_nn_out = nullptr;                        // [G]
+    std::vector<uint32_t> h_nn_off;                           // [G + 1]
+    std::vector<int64_t> h_nn_new;                            // [G] n_new of the last eval (list lengths)
+    bool nn_valid = false;                                    // esc_new_nodes_eval results current
 };
 
 namespace esc {
@@ -646,6 +654,14 @@ void release_placement(esc_ctx* c) {
     c->h_soft.clear();
     c->h_hard.clear();
     c->placed = c->node_removal = c->rm_valid = false;
+}
+
+// The instantiation-time fact and the new-node pass's buffers: part of the node table.
+void release_new_nodes(esc_ctx* c) {
+    dfree(c->d_inst); dfree(c->d_nn_since); dfree(c->d_nn_off); dfree(c->d_nn_list); dfree(c->d_nn_out);
+    c->h_nn_off.clear();
+    c->h_nn_new.clear();
+    c->nn_valid = false;
 }
 
 void release_sort(esc_ctx* c) {
@@ -1553,6 +1569,7 @@ int32_t esc_ctx_destroy(esc_ctx* c) {
         release_work(c);
         release_sort(c);
         release_placement(c);
+        release_new_nodes(c);
         for (auto& b : c->pods) b.release();
         c->nodes.release();
         dfree(c->d_dry); dfree(c->d_params);
@@ -1842,6 +1859,7 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     release_work(c);
     release_sort(c);
     release_placement(c);
+    c->nn_valid = false;                             // a reload: the new-node eval is no longer current
     for (auto& b : c->pods) b.release();
     c->pods.assign(c->n_replicas, PodBuf());
     for (int r = 0; r < c->n_replicas; ++r) {
@@ -2068,12 +2086,22 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
     std::vector<uint32_t> trk_start(std::max<int64_t>(n + (sf > 0 ? (int64_t)std::ceil((double)n * sf) + 64 : 0), 1),
                                     NONE);
     for (int64_t k = s->n_trk - 1; k >= 0; --k) trk_start[s->trk_node[k]] = (uint32_t)k;
+    // the new-node pass's list offsets: a group's list holds at most its pair's entry capacity
+    // (checked here, from host data alone: a refused load leaves the previous snapshot intact)
+    std::vector<uint32_t> nn_off((size_t)G + 1, 0);
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint32_t q = c->gi.gpair[g];
+        const uint64_t end = (uint64_t)nn_off[g] + (piece_off[pp_off[q + 1]] - piece_off[pp_off[q]]);
+        if (end >= 0xFFFFFFFFull) return ESC_E_LIMIT;
+        nn_off[g + 1] = (uint32_t)end;
+    }
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     drop_graphs(c);
     release_work(c);
     release_sort(c);
     release_placement(c);
+    release_new_nodes(c);
     c->nodes.release();
     // capacity for added nodes (esc_nodes_add): table slots and extra-label words
     const int64_t n_cap = n + (sf > 0 ? (int64_t)std::ceil((double)n * sf) + 64 : 0);
@@ -2151,6 +2179,16 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
         HIP_TRY(dalloc(&b.gnode, gn.size()));
         HIP_TRY(hipMemcpy(b.gnode, gn.data(), gn.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
         c->h_gnode.swap(gn);
+    }
+    {   // the instantiation-time fact (every slot unknown, the spare ones included) and the
+        // new-node pass's lists: a group's list holds at most its pair's entry capacity
+        std::vector<int64_t> unknown((size_t)std::max<int64_t>(n_cap, 1), INT64_MIN);
+        HIP_TRY(dalloc(&c->d_inst, unknown.size()));
+        HIP_TRY(hipMemcpy(c->d_inst, unknown.data(), unknown.size() * 8, hipMemcpyHostToDevice));
+        c->h_nn_off.swap(nn_off);
+        HIP_TRY(dalloc(&c->d_nn_off, G)); HIP_TRY(dalloc(&c->d_nn_since, G)); HIP_TRY(dalloc(&c->d_nn_out, G));
+        HIP_TRY(dalloc(&c->d_nn_list, std::max<uint32_t>(c->h_nn_off[G], 1)));
+        if (G) HIP_TRY(hipMemcpy(c->d_nn_off, c->h_nn_off.data(), (size_t)G * 4, hipMemcpyHostToDevice));
     }
     // host mirrors for node events (table slots up to the capacity)
     c->pair_next.assign(n_gp, 0);
@@ -3384,7 +3422,7 @@ bool region_remove(esc_ctx* c, uint32_t g, uint32_t j, Patches& R) {
 // the node table, the nodes' pair-major K2 entries, allNodes[0]'s cached allocatable,
 // and the K5 region copies (looked up by creation time: no re-listing).
 int32_t patch_nodes(esc_ctx* c, const std::vector<int64_t>& ids) {
-    c->rm_valid = false;
+    c->rm_valid = c->nn_valid = false;
     Patches P;
     bool first_changed = false;
     for (int64_t j : ids) {
@@ -3910,6 +3948,7 @@ int32_t esc_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out) {
         c->xl_used += s->n_xl;
         c->n_nodes += n;
         c->rm_valid = false;            // the placement stays: every table slot has a run and facts
+        c->nn_valid = false;            // (the new slots' instantiation times are unknown since the load)
         int32_t rc = apply_patches(c, P, {node_targets(c)});
         if (rc) return rc;
         if (first_changed)
@@ -3982,8 +4021,23 @@ int32_t esc_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n) {
             HIP_TRY(hipMemcpy(c->nodes.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
         // the placement stays: a deleted node's entries are absent (K6 / K7 skip them) and its
         // pods' PodRefs stay in its run until they are rebound or deleted
-        c->rm_valid = false;
-        return patch_nodes(c, del);
+        c->rm_valid = c->nn_valid = false;
+        // the slots' instantiation times go back to unknown (a later node inherits nothing):
+        // queued on the stream ahead of the patches, whose wait covers it
+        int64_t* d_ids = nullptr;
+        if (c->d_inst) {
+            HIP_TRY(dalloc(&d_ids, del.size()));
+            hipError_t e = hipMemcpyAsync(d_ids, del.data(), del.size() * 8, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = launch_node_inst(c->d_inst, d_ids, nullptr, (int64_t)del.size(), c->stream);
+            if (e != hipSuccess) {
+                dfree(d_ids);
+                return fail_hip(e, "esc_nodes_delete: instantiation-time reset");
+            }
+        }
+        const int32_t rc = patch_nodes(c, del);
+        if (d_ids && rc != ESC_OK) hipStreamSynchronize(c->stream);   // (patch_nodes gave up before its wait)
+        dfree(d_ids);
+        return rc;
     });
 }
 
@@ -4107,7 +4161,7 @@ int32_t relabel_apply(esc_ctx* c, const int64_t* ids, const esc_node_soa* s, con
     const uint32_t n_gp = c->gi.n_gp;
     hipSetDevice(c->device);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->rm_valid = false;
+    c->rm_valid = c->nn_valid = false;
     // the nodes' pods leave the occupancy words of their current entries
     std::vector<uint32_t> opos, onode;
     if (c->placed) {
@@ -4347,7 +4401,7 @@ int32_t esc_tracker_update(esc_ctx* c, int32_t group, const int64_t* add, int64_
             if (f != c->h_nflags[j]) { c->h_nflags[j] = f; flip.push_back(j); }
         }
         c->sorted = false;
-        c->rm_valid = false;
+        c->rm_valid = c->nn_valid = false;
         if (!flip.empty()) return patch_nodes(c, touched);     // node table + entries + K5 copies
         // the K5 copies carry each dry membership's tracker bit: patch the touched nodes'
         rc = patch_regions(c, touched);
@@ -4646,6 +4700,87 @@ int32_t esc_removal_nodes(esc_ctx* c, int32_t g, int64_t* idx, int64_t cap, int6
     // K7 lists them in entry order: snapshot order, except behind a relabelled node's entry
     std::sort(v.begin(), v.end());
     for (int64_t k = 0; k < n; ++k) idx[k] = v[k];
+    return ESC_OK;
+}
+
+// ------------------------------------------------ newly registered nodes
+// esc_nodes_instantiated: the instantiation time of a handful of nodes (the host asked the
+// cloud provider about the nodes the last eval listed as unknown), in place: the batch is
+// staged with one copy — ids, then the times — and scattered by one launch.
+int32_t esc_nodes_instantiated(esc_ctx* c, const int64_t* ids, int64_t n, const int64_t* inst_ns) {
+    if (c && c->multi) return esc::multi_nodes_instantiated(c, ids, n, inst_ns);
+    if (!c || n < 0 || (n > 0 && (!ids || !inst_ns))) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nodes_loaded || !c->d_inst || (c->stale & STALE_NODES)) return ESC_E_STATE;
+    if (n == 0) return ESC_OK;
+    for (int64_t i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= c->n_nodes || (c->h_nflags[ids[i]] & ESC_NF_ABSENT)) return ESC_E_INVAL;
+    {
+        std::vector<int64_t> seen(ids, ids + n);           // one event per node: every element has one writer
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return ESC_E_INVAL;
+    }
+    hipSetDevice(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int64_t> stage((size_t)n * 2);
+    std::memcpy(stage.data(), ids, (size_t)n * 8);
+    std::memcpy(stage.data() + n, inst_ns, (size_t)n * 8);
+    int64_t* d = nullptr;
+    HIP_TRY(dalloc(&d, stage.size()));
+    if (hipMemcpy(d, stage.data(), stage.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(d);                                          // nothing written yet: not stale
+        return ESC_E_HIP;
+    }
+    c->nn_valid = false;
+    return guarded(c, STALE_NODES, [&]() -> int32_t {
+        hipError_t e = launch_node_inst(c->d_inst, d, d + n, n, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        dfree(d);
+        HIP_TRY(e);
+        return ESC_OK;
+    });
+}
+
+// k_new_nodes over every group; the records come back by one copy.
+int32_t esc_new_nodes_eval(esc_ctx* c, const int64_t* since_ns, esc_new_nodes* out) {
+    if (c && c->multi) return esc::multi_new_nodes_eval(c, since_ns, out);
+    if (!c || !since_ns || !out) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nodes_loaded || !c->d_inst || (c->stale & STALE_NODES)) return ESC_E_STATE;
+    const int32_t G = c->gi.G;
+    c->nn_valid = false;
+    if (G <= 0) { c->nn_valid = true; return ESC_OK; }
+    hipSetDevice(c->device);
+    NewNodesDev w;
+    w.inst_ns = c->d_inst; w.since = c->d_nn_since; w.list_off = c->d_nn_off; w.list = c->d_nn_list; w.out = c->d_nn_out;
+    c->h_nn_new.assign(since_ns, since_ns + G);              // (the staging copy; the counts replace it below)
+    HIP_TRY(hipMemcpyAsync(c->d_nn_since, c->h_nn_new.data(), (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_new_nodes(node_dev(c), group_dev(c), w, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_nn_out, (size_t)G * sizeof(esc_new_nodes), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int32_t g = 0; g < G; ++g) c->h_nn_new[g] = out[g].n_new;
+    c->nn_valid = true;
+    return ESC_OK;
+}
+
+int32_t esc_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known, int64_t cap, int64_t* n_out) {
+    if (c && c->multi) return esc::multi_new_nodes_list(c, g, idx, known, cap, n_out);
+    if (!c || !n_out || g < 0 || g >= c->gi.G || cap < 0 || (cap > 0 && (!idx || !known))) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nn_valid) return ESC_E_STATE;
+    const int64_t n = c->h_nn_new[g];
+    *n_out = n;
+    if (n > cap) return ESC_E_LIMIT;
+    if (!n) return ESC_OK;
+    std::vector<uint32_t> v(n);
+    hipSetDevice(c->device);
+    HIP_TRY(hipMemcpy(v.data(), c->d_nn_list + c->h_nn_off[g], n * 4, hipMemcpyDeviceToHost));
+    // the pass lists them in entry order: snapshot order, except behind a relabelled node's entry
+    std::sort(v.begin(), v.end(), [](uint32_t a, uint32_t b) { return (a & ~NN_UNKNOWN) < (b & ~NN_UNKNOWN); });
+    for (int64_t k = 0; k < n; ++k) {
+        idx[k] = v[k] & ~NN_UNKNOWN;
+        known[k] = (v[k] & NN_UNKNOWN) ? 0 : 1;
+    }
     return ESC_OK;
 }
 

@@ -85,6 +85,10 @@ class EventQueue:
         self.flushes = 0
         self.applied = {k: 0 for k in KINDS}
         self.touched_nodes = False                 # the last flush added nodes or reloaded
+        # node name -> the cloud instance's instantiation time (Unix ns), as the controller's
+        # new-node pass learned it (GetInstance, controller.go:173): the device holds the
+        # same fact per slot, and only a reload loses it there
+        self.inst_ns: dict[str, int] = {}
 
     # ------------------------------------------------------------------ ingest
     def _index_pod(self, key, old, new):
@@ -122,6 +126,7 @@ class EventQueue:
 
     def node_delete(self, node):
         name = node if isinstance(node, str) else node.get("name", "")
+        self.inst_ns.pop(name, None)               # a node back under this name is a new instance
         if self.nodes.pop(name, None) is not None:
             self._dirty_nodes[name] = True
 
@@ -287,3 +292,8 @@ class EventQueue:
         self._loaded = True
         self.touched_nodes = True
         self.reloads += 1
+        # the load left every instantiation time unknown: the known ones go back in one call
+        known = [m for m in order_n if m in self.inst_ns]
+        if known:
+            ctx.nodes_instantiated(np.array([self._node_idx[m] for m in known], np.int64),
+                                   np.array([self.inst_ns[m] for m in known], np.int64))

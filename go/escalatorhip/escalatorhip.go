@@ -830,3 +830,71 @@ func (x *Context) DeleteList(g int, n int64) ([]int64, error) {
 	}
 	return idx[:n], nil
 }
+
+// ------------------------------------------------- newly registered nodes
+
+// NewNodes is calculateNewNodeMetrics' outcome for one group (controller.go:157-189):
+// Observed is the reference's countNewNodes, Bucket the non-cumulative counts of
+// NodeGroupNodeRegistrationLag's 29 bounds (metrics.go:190) and +Inf.
+type NewNodes struct {
+	New, Observed, LagSumNs int64
+	LagOverflow              bool
+	Bucket                   [C.ESC_NN_BUCKETS]uint32
+}
+
+// SetInstantiated records the cloud instances' instantiation times (Unix ns) of the nodes
+// ids — instance.InstantiationTime() of the GetInstance answers (controller.go:173-177) —
+// in place; the device keeps them until the node is deleted or the node table reloaded.
+func (x *Context) SetInstantiated(ids []int64, t []int64) error {
+	if len(ids) != len(t) {
+		return fmt.Errorf("escalatorhip: %d ids for %d instantiation times", len(ids), len(t))
+	}
+	return rcErr("esc_nodes_instantiated", C.esc_nodes_instantiated(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))),
+		C.int64_t(len(ids)), (*C.int64_t)(unsafe.Pointer(ptr(t)))))
+}
+
+// NewNodeMetrics evaluates calculateNewNodeMetrics' loop for every group at once.  since[g]
+// is the group's lastScaleOut in Unix ns (math.MinInt64 for the zero time.Time), or
+// math.MaxInt64 for a group that does not reach controller.go:325 this scan or whose
+// scaleDelta is not positive (:165).  NewNodeList(g) then lists the group's new nodes.
+func (x *Context) NewNodeMetrics(since []int64) ([]NewNodes, error) {
+	if len(since) != len(x.groups) {
+		return nil, fmt.Errorf("escalatorhip: NewNodeMetrics needs one since time per group (%d)", len(x.groups))
+	}
+	out := make([]C.esc_new_nodes, len(x.groups))
+	rc := C.esc_new_nodes_eval(x.c, (*C.int64_t)(unsafe.Pointer(ptr(since))), ptr(out))
+	if rc != C.ESC_OK {
+		return nil, rcErr("esc_new_nodes_eval", rc)
+	}
+	res := make([]NewNodes, len(out))
+	for g, r := range out {
+		res[g] = NewNodes{New: int64(r.n_new), Observed: int64(r.n_observed), LagSumNs: int64(r.lag_sum_ns),
+			LagOverflow: r.flags&C.ESC_NN_LAG_OVERFLOW != 0}
+		for k := range res[g].Bucket {
+			res[g].Bucket[k] = uint32(r.bucket[k])
+		}
+	}
+	return res, nil
+}
+
+// NewNodeList returns group g's new nodes of the last NewNodeMetrics (snapshot indices,
+// ascending) and, per node, whether its instantiation time was known: the host asks the
+// cloud provider about the others (GetInstance) and hands the answers to SetInstantiated.
+func (x *Context) NewNodeList(g int) ([]int64, []bool, error) {
+	var n C.int64_t
+	rc := C.esc_new_nodes_list(x.c, C.int32_t(g), nil, nil, 0, &n)
+	if rc != C.ESC_OK && rc != C.ESC_E_LIMIT {
+		return nil, nil, rcErr("esc_new_nodes_list", rc)
+	}
+	idx, known := make([]int64, n), make([]uint8, n)
+	rc = C.esc_new_nodes_list(x.c, C.int32_t(g), (*C.int64_t)(unsafe.Pointer(ptr(idx))),
+		(*C.uint8_t)(unsafe.Pointer(ptr(known))), n, &n)
+	if rc != C.ESC_OK {
+		return nil, nil, rcErr("esc_new_nodes_list", rc)
+	}
+	out := make([]bool, len(known))
+	for i, k := range known {
+		out[i] = k != 0
+	}
+	return idx, out, nil
+}

@@ -605,6 +605,76 @@ int32_t esc_reap_finish(esc_ctx* ctx, int64_t now_unix_ns, const int64_t* soft_g
                         const int64_t* hard_grace_ns, esc_removal* out);
 int32_t esc_removal_nodes(esc_ctx* ctx, int32_t group, int64_t* idx_out, int64_t cap, int64_t* n_out);
 
+/* ------------------------------------- newly registered nodes and their registration lag
+ * calculateNewNodeMetrics (pkg/controller/controller.go:157-189, called at :325 for every
+ * unlocked group) for every group at once: the per-node loop over the group's NodeInfoMap
+ * that joins each node against the group's lastScaleOut (`creation > lastScaleOut`, :171),
+ * counts the matches for the comparison with the previous delta (:185) and observes
+ * NodeGroupNodeRegistrationLag (pkg/metrics/metrics.go:185-193, buckets 60, 120, ..., 1740 s)
+ * with `creation - instantiation` of each match (:177-179).  The cloud call of that loop
+ * (GetInstance, :173) stays on the host: it is asked about the nodes the pass lists as
+ * unknown only, once per node (an instance's launch time never changes), and its answers
+ * are kept on the device as a per-node fact.
+ *
+ * The fact, inst_ns: one int64 per node-table slot, Unix ns; INT64_MIN = unknown (never
+ * looked up, or GetInstance failed).  It belongs to the node table: esc_load_nodes allocates
+ * it with every slot unknown (spare slots included; no placement is needed),
+ * esc_nodes_add leaves the new slots unknown, esc_nodes_delete resets the slot (a later node
+ * in it inherits nothing), esc_nodes_relabel and esc_nodes_update keep it.
+ * esc_nodes_instantiated patches it in place with esc_nodes_facts' contract: one staged copy
+ * and one launch, complete before returning, all or nothing — ESC_E_INVAL with nothing
+ * applied for a null argument with n > 0, an id outside the table, an ESC_NF_ABSENT slot or a
+ * repeated id; n == 0 is ESC_OK; ESC_E_STATE before esc_load_nodes and while the node side is
+ * stale.  A multi-device context applies the batch on every device, and every rank of a
+ * sharded job makes the call (each holds the whole node table).
+ *
+ * esc_new_nodes_eval, per group g (every live entry of its label pair — untainted, tainted
+ * and cordoned nodes alike: NodeInfoMap is built from allNodes, controller.go:259;
+ * ESC_NF_ABSENT entries are skipped; dry mode makes no difference):
+ *   new      : created_ns > since_unix_ns[g], strictly (Go's saturating Sub(...) > 0 has the
+ *              same sign);
+ *   lag      : created_ns - inst_ns, saturated to the int64 range like Go's Time.Sub;
+ *   bucket   : the first k with lag <= 60e9 * (k + 1) ns, else the +Inf bucket 29 — an
+ *              integer compare.  Prometheus picks the first bound >= lag.Seconds(), so a
+ *              negative lag lands in bucket 0.  The integer compare is exact with respect to
+ *              Duration.Seconds() at these magnitudes: Seconds() is float64(sec) +
+ *              float64(nsec) / 1e9 with sec < 2^53, which is monotone in the ns value and
+ *              equals the integer bound exactly when nsec == 0, so `lag_ns <= bound_ns`
+ *              and `Seconds() <= bound_s` agree for every bound (tests/newnode_literal.py
+ *              checks the two rules against each other);
+ *   lag_sum_ns: the exact integer sum over the observed nodes (accumulated split lo32 / hi,
+ *              so it cannot wrap unnoticed); ESC_NN_LAG_OVERFLOW is set when the total leaves
+ *              int64 (the field then holds its low 64 bits).  It replaces the histogram's
+ *              float64 sum, which follows Go's random map order and is not reproducible:
+ *              lag_sum_ns is not bit-comparable to it.
+ * The pass uses no global atomics: records and lists are deterministic.  Every rank and every
+ * device holds the whole node table, so an eval answers every group on any rank with no
+ * exchange (no ESC_ST_NOT_OWNED); a multi-device context evaluates on one device.
+ * ESC_E_STATE before esc_load_nodes and while the node side is stale.  One wave walks one
+ * group (as esc_try_remove's K7): very large groups are not split.
+ * Every node event (add, delete, update, relabel, tracker change), every reload
+ * (esc_load_pods, esc_load_nodes) and every esc_nodes_instantiated call makes the last eval
+ * not current: esc_new_nodes_list then returns ESC_E_STATE until the next eval. */
+int32_t esc_nodes_instantiated(esc_ctx* ctx, const int64_t* ids, int64_t n, const int64_t* inst_unix_ns);
+
+#define ESC_NN_BUCKETS 30            /* 29 bounds 60..1740 s (metrics.go:190) and +Inf */
+#define ESC_NN_LAG_OVERFLOW 1        /* flags: the lag sum left int64 */
+typedef struct esc_new_nodes {
+    int64_t  n_new;                  /* nodes of the group with creation > since                  */
+    int64_t  n_observed;             /* of them, instantiation known: the reference's countNewNodes */
+    int64_t  lag_sum_ns;             /* sum over the observed nodes of creation - instantiation   */
+    int64_t  flags;
+    uint32_t bucket[ESC_NN_BUCKETS]; /* non-cumulative: bucket k = first k with lag <= 60 s*(k+1) */
+} esc_new_nodes;                     /* 152 bytes */
+
+/* since_unix_ns[g]: lastScaleOut of group g; INT64_MIN = the zero time.Time (every node is newer);
+   INT64_MAX = group not evaluated this scan (zero record, empty list).  Synchronous. */
+int32_t esc_new_nodes_eval(esc_ctx* ctx, const int64_t* since_unix_ns, esc_new_nodes* out);
+/* group g's new nodes from the last eval: snapshot indices (ascending), and known[i] != 0 when
+   the node's instantiation time was known.  idx NULL / cap 0 sizes (*n_out; known_out may be
+   NULL too); ESC_E_LIMIT when cap is short. */
+int32_t esc_new_nodes_list(esc_ctx* ctx, int32_t group, int64_t* idx_out, uint8_t* known_out, int64_t cap, int64_t* n_out);
+
 /* ----------------------------------------------------------------- ordering
  * K5: per-group creation-time order of the context's node shard (a18/a19):
  *   which 0: untainted members oldest-first (taintOldestN,   scale_down.go:171)
