@@ -82,6 +82,17 @@ class NewNodes(C.Structure):
                 ("bucket", u32 * ESC_NN_BUCKETS)]
 
 
+AUDIT_CHECKS = ["ENTRY", "FIRST", "REGION", "OCC", "TOUCH", "TRACKER", "MIRROR"]   # ESC_AUD_*
+
+
+class AuditCheck(C.Structure):
+    _fields_ = [("n_checked", i64), ("n_bad", i64), ("first_bad", i64)]
+
+
+class AuditReport(C.Structure):
+    _fields_ = [("ran", u32), ("skipped", u32), ("check", AuditCheck * len(AUDIT_CHECKS))]
+
+
 class KV(C.Structure):
     _fields_ = [("key", cstr), ("value", cstr)]
 
@@ -194,6 +205,7 @@ _SIGS = {
     "esc_nodes_instantiated": (i32, [VP, P(i64), i64, P(i64)]),
     "esc_new_nodes_eval": (i32, [VP, P(i64), P(NewNodes)]),
     "esc_new_nodes_list": (i32, [VP, i32, P(i64), P(C.c_uint8), i64, P(i64)]),
+    "esc_audit": (i32, [VP, u32, P(AuditReport)]),
     "esc_set_metrics": (i32, [VP, i32]),
     "esc_metrics_results": (i32, [VP, P(GroupMetrics)]),
     "esc_use_graph": (i32, [VP, i32]),

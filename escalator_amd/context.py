@@ -596,6 +596,25 @@ class Context:
                 "esc_new_nodes_list")
         return idx[:n.value], known[:n.value]
 
+    # ------------------------------------------------------------- audit
+    def audit(self, checks=None) -> dict:
+        """esc_audit: the resident snapshot's derived state recomputed from its primary tables.
+        checks: names from ``_lib.AUDIT_CHECKS`` (None = all).  Returns check name ->
+        {n_checked, n_bad, first_bad} for the checks that ran, plus ``"skipped"``: the names of
+        the asked checks whose state is not resident (OCC without a placement, REGION without
+        an age index, TOUCH before the first decision's K1 plan)."""
+        names = L.AUDIT_CHECKS
+        mask = 0
+        for c in (checks or ()):
+            mask |= 1 << names.index(c)
+        rep = L.AuditReport()
+        L.check(self.lib.esc_audit(self.handle, mask, C.byref(rep)), "esc_audit")
+        out = {n: {"n_checked": int(rep.check[k].n_checked), "n_bad": int(rep.check[k].n_bad),
+                   "first_bad": int(rep.check[k].first_bad)}
+               for k, n in enumerate(names) if (rep.ran >> k) & 1}
+        out["skipped"] = [n for k, n in enumerate(names) if (rep.skipped >> k) & 1]
+        return out
+
     # ------------------------------------------------------------- ordering
     def sort_nodes(self):
         L.check(self.lib.esc_sort_nodes(self.handle), "esc_sort_nodes")

@@ -453,15 +453,28 @@ class ResidentController(Controller):
     the list of names (controller.go:35) and is mirrored onto the device with
     ``tracker_update`` after the walks; after a flush that added nodes or reloaded, tracked
     names the device does not track (a reload drops the tracker, a node back under a tracked
-    name has a new index) are re-added; a tracked name whose node is gone stays in the list."""
+    name has a new index) are re-added; a tracked name whose node is gone stays in the list.
+
+    ``audit_every=k`` (0 = never): on every k-th scan, after the flush and before the decision,
+    ``ctx.audit()`` checks the snapshot's derived state against its primary tables; a mismatch
+    reloads the snapshot once from the queue's object store (``events.reload_causes`` gets
+    ``"audit:<check>"``) and counts in ``audit_failures``; ``audits`` counts the passes."""
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
-                 selection_slack: int = 4, spare: float = 0.5):
+                 selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0):
         super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
                          selection_slack=selection_slack)
         from .events import EventQueue
         self.spare = float(spare)
         self.events = EventQueue(spare=self.spare)
+        # the resync of the derived state (the reference's informers resync hourly,
+        # pkg/k8s/cache.go:27,48): every audit_every-th scan audits the snapshot after the flush
+        # and reloads it once when a check finds a mismatch; 0 = never
+        self.audit_every = int(audit_every)
+        self.scans = 0
+        self.audits = 0
+        self.audit_failures = 0
+        self.last_audit = None
 
     def _learned(self, name: str, j: int, t: int):
         """The queue keeps the cache: it drops a name on node_delete and re-sends the cache
@@ -479,8 +492,22 @@ class ResidentController(Controller):
             if missing:
                 self.ctx.tracker_update(g, add=missing)
 
+    def _audit(self):
+        """Context.audit on the flushed snapshot; a mismatch makes the queue reload once (cause
+        "audit:<the first failing check>"), after which the trackers are re-added as after any
+        reload."""
+        self.last_audit = rep = self.ctx.audit()
+        self.audits += 1
+        bad = [n for n in L.AUDIT_CHECKS if n in rep and rep[n]["n_bad"] > 0]
+        if bad:
+            self.audit_failures += 1
+            self.events.reload(self.ctx, "audit:" + bad[0])
+
     def run_once(self) -> list[dict]:
         self.events.flush(self.ctx)
+        self.scans += 1
+        if self.audit_every and self.scans % self.audit_every == 0:
+            self._audit()
         if self.events.touched_nodes:
             self._sync_trackers()
         now = self.clock()

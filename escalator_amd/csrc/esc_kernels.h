@@ -572,6 +572,39 @@ hipError_t launch_new_nodes(const NodeDev& n, const GroupDev& g, const NewNodesD
 // every listed id when ev_inst is null; one event per thread (ids unique).
 hipError_t launch_node_inst(int64_t* inst_ns, const int64_t* ids, const int64_t* ev_inst, int64_t n, hipStream_t st);
 
+// esc_audit: read-only checks of the derived state against its primary tables.  Every check
+// adds to its row of `rep` ([ESC_AUD_N][AW_K] int64, AW_FIRST preset to INT64_MAX): counts
+// summed and the lowest offending id, reduced per wave, then one relaxed agent-scope atomic per
+// wave and word — a deterministic report.  A derived word may be wrong, so every index read
+// from one is bounds-checked before it is used (n_cap, n_entries, ne_len, n_trk).
+enum AuditWord : int { AW_CHECKED = 0, AW_BAD, AW_FIRST, AW_K };
+struct AuditDev {
+    int64_t* rep;
+    uint32_t* pair_cnt;        // [n_gp] live entries found per group pair (the host compares pair_live)
+    uint32_t* memb_cnt;        // [G] live memberships found per region
+    int64_t n_cap;             // node-table capacity (slots of flags / cpu / mem / label0 / trk_start)
+    int64_t n_entries;
+    const uint32_t* e_pair;    // [n_entries] pair of each entry (with a placement), or null
+    const uint32_t* ne_off;    // node -> entries map: [n_cap + 1]
+    const uint32_t* ne_pos;
+    int64_t ne_len;            // words of ne_pos
+};
+// ENTRY, forward: one block per group pair over its entry range (K7's walk, four waves wide).
+hipError_t launch_audit_entries(const NodeDev& n, const GroupDev& g, const AuditDev& a, hipStream_t st);
+// ENTRY, reverse: one thread per node slot through the node -> entries map.
+hipError_t launch_audit_node_entries(const NodeDev& n, const GroupDev& g, const AuditDev& a, hipStream_t st);
+// FIRST: one wave per listed group over its pair's entries (k_try_remove's walk).
+hipError_t launch_audit_first(const NodeDev& n, const GroupDev& g, const GroupList& list, const AuditDev& a,
+                              hipStream_t st);
+// REGION: one block per group over its region [pstart[g], pstart[g + 1]) with plen[g] memberships.
+hipError_t launch_audit_regions(const NodeDev& n, const GroupDev& g, const uint32_t* pstart, const uint32_t* plen,
+                                const uint32_t* g_memb, const AuditDev& a, hipStream_t st);
+// OCC: the recounted words (`fresh`, [2][n_entries]) against the maintained ones over the live entries.
+hipError_t launch_audit_occ(const NodeDev& n, const GroupDev& g, const AuditDev& a, const uint32_t* fresh,
+                            const uint32_t* kept, hipStream_t st);
+// TRACKER: one thread per node slot and per tracker entry.
+hipError_t launch_audit_tracker(const NodeDev& n, const GroupDev& g, const AuditDev& a, hipStream_t st);
+
 
 // Ordering (K5), see esc_kernels.hip: the age index (once per snapshot) and the per-decision
 // (group, class) partition.

@@ -3258,6 +3258,223 @@ __global__ __launch_bounds__(64) void k_new_nodes(NodeDev N, GroupDev G, NewNode
     }
 }
 
+// ===================================================================== audit (esc_audit)
+// Read-only: each kernel recomputes a derived structure from its primary one and adds what it
+// found to its row of the report.  The derived words are the ones under suspicion, so no index
+// read from one is used before it is checked against its array's size.
+namespace {
+__device__ __forceinline__ int64_t wave_min64(int64_t v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = imin64(v, (int64_t)__shfl_xor((unsigned long long)v, o, 64));
+    return v;
+}
+// Called by every lane of a wave: the wave's counts summed, its lowest offender, one relaxed
+// agent-scope atomic per word from lane 0 (sums and a minimum: any arrival order, one report).
+__device__ __forceinline__ void audit_emit(int64_t* __restrict__ rep, int check, uint32_t checked, uint32_t bad,
+                                           int64_t first) {
+    const uint32_t c = wave_total32(checked), b = wave_total32(bad);
+    first = wave_min64(first);
+    if ((threadIdx.x & 63) != 0) return;
+    int64_t* r = rep + check * AW_K;
+    if (c) __hip_atomic_fetch_add(r + AW_CHECKED, (int64_t)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (b) {
+        __hip_atomic_fetch_add(r + AW_BAD, (int64_t)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_min(r + AW_FIRST, first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+constexpr uint32_t NF_CLASS = ESC_NF_UNSCHED | ESC_NF_TAINTED | ESC_NF_TRACKED | ESC_NF_ABSENT;
+}  // namespace
+
+// ENTRY, forward.  Block q walks group pair q's entries [e0, e1): a live entry (its node is in
+// the table and not absent) must sit on a node that carries q and hold that node's class bits
+// and allocatable in the three arrays and the packed record; an entry without a live node must
+// be flagged absent.
+__global__ __launch_bounds__(256) void k_audit_entries(NodeDev N, GroupDev G, AuditDev A) {
+    const uint32_t q = blockIdx.x;
+    const int64_t e0 = N.piece_off[N.pp_off[q]], e1 = N.piece_off[N.pp_off[q + 1]];
+    uint32_t chk = 0, bad = 0;
+    int64_t first = INT64_MAX;
+    for (int64_t b = e0; b < e1; b += 256) {
+        const int64_t e = b + threadIdx.x;
+        if (e >= e1) continue;
+        const uint32_t f = N.e_flags[e], j = N.e_node[e];
+        bool wrong;
+        if (j == NONE) {
+            wrong = !(f & ESC_NF_ABSENT);                              // spare or retired
+        } else if ((int64_t)j >= A.n_cap) {
+            wrong = true;
+        } else {
+            const uint32_t nf = N.flags[j];
+            if (nf & ESC_NF_ABSENT) {
+                wrong = !(f & ESC_NF_ABSENT);                          // its node was deleted
+            } else {
+                ++chk;
+                const int64_t cpu = N.cpu[j], mem = N.mem[j];
+                wrong = ((f ^ nf) & NF_CLASS) != 0 || N.e_cpu[e] != cpu || N.e_mem[e] != mem || !node_has_pair(N, j, q);
+                if (N.e_pk) {
+                    const uint4 pk = N.e_pk[e];
+                    wrong |= ((pk.x ^ nf) & NF_CLASS) != 0 || pk.y != (uint32_t)cpu ||
+                             (((uint64_t)pk.w << 32) | pk.z) != (uint64_t)mem;
+                }
+                if (A.e_pair) wrong |= A.e_pair[e] != q;
+            }
+        }
+        if (wrong) { ++bad; first = imin64(first, e); }
+    }
+    const uint32_t live = wave_total32(chk);
+    if ((threadIdx.x & 63) == 0 && live)
+        __hip_atomic_fetch_add(A.pair_cnt + q, live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    audit_emit(A.rep, ESC_AUD_ENTRY, chk, bad, first);
+}
+
+// ENTRY, reverse.  Thread j: every group pair the live node j carries is found through the
+// node -> entries map at exactly one entry of that pair whose node is j (the map also lists
+// entries a relabel retired; they name no node).  Offender: the entry found, else the pair's first.
+__global__ __launch_bounds__(256) void k_audit_node_entries(NodeDev N, GroupDev G, AuditDev A) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0;
+    int64_t first = INT64_MAX;
+    if (j < A.n_cap && !(N.flags[j] & ESC_NF_ABSENT)) {
+        const uint32_t k0 = A.ne_off[j], k1 = A.ne_off[j + 1];
+        const bool map_ok = k0 <= k1 && (int64_t)k1 <= A.ne_len;
+        const uint32_t nx = nf_xlbl(N.flags[j]), xo = N.xl_off[j];
+        for (uint32_t x = 0; x <= nx; ++x) {
+            const uint32_t q = x == 0 ? N.label0[j] : N.xl[xo + x - 1];
+            if (q >= G.n_gp) continue;
+            const int64_t e0 = N.piece_off[N.pp_off[q]], e1 = N.piece_off[N.pp_off[q + 1]];
+            uint32_t hits = 0;
+            int64_t at = e0;
+            for (uint32_t k = k0; map_ok && k < k1; ++k) {
+                const int64_t e = A.ne_pos[k];
+                if (e >= e0 && e < e1 && e < A.n_entries && N.e_node[e] == (uint32_t)j) { ++hits; at = e; }
+            }
+            if (hits != 1) { ++bad; first = imin64(first, at); }
+        }
+    }
+    audit_emit(A.rep, ESC_AUD_ENTRY, 0, bad, first);
+}
+
+// FIRST.  One wave per group over its pair's entries, as K7 walks them: the lowest live node
+// of the pair is the group's cached allNodes[0] (controller.go:207-211), with its allocatable.
+__global__ __launch_bounds__(64) void k_audit_first(NodeDev N, GroupDev G, GroupList L, AuditDev A) {
+    const int32_t g = L.ids ? (int32_t)L.ids[blockIdx.x] : L.first + (int32_t)blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint32_t q = G.gpair[g];
+    const int64_t e0 = N.piece_off[N.pp_off[q]], e1 = N.piece_off[N.pp_off[q + 1]];
+    int64_t lowest = INT64_MAX;
+    for (int64_t e = e0 + lane; e < e1; e += 64) {
+        const uint32_t j = N.e_node[e];
+        if (j != NONE && (int64_t)j < A.n_cap && !(N.flags[j] & ESC_NF_ABSENT)) lowest = imin64(lowest, (int64_t)j);
+    }
+    lowest = wave_min64(lowest);
+    bool wrong = false;
+    if (lane == 0) {
+        const GroupNode x = N.gnode[g];
+        wrong = x.first != lowest;
+        if (!wrong && lowest != INT64_MAX) wrong = x.first_cpu != N.cpu[lowest] || x.first_mem != N.mem[lowest];
+    }
+    audit_emit(A.rep, ESC_AUD_FIRST, lane == 0 ? 1u : 0u, wrong ? 1u : 0u, wrong ? (int64_t)g : INT64_MAX);
+}
+
+// REGION.  Block g over its region: the first plen[g] words are memberships — a node of the
+// table that carries the group's pair, its class nibble the node's (the tracker bit resolved
+// for a dry group, as the listing and the patches write it; a deleted node's word stays in
+// place with the absent nibble alone) — non-decreasing in (creation time, node); the rest of
+// the region is padding.
+__global__ __launch_bounds__(256) void k_audit_regions(NodeDev N, GroupDev G, const uint32_t* __restrict__ pstart,
+                                                       const uint32_t* __restrict__ plen,
+                                                       const uint32_t* __restrict__ g_memb, AuditDev A) {
+    const int32_t g = blockIdx.x;
+    const int64_t a = pstart[g], cap = (int64_t)pstart[g + 1] - a;
+    const uint32_t q = G.gpair[g];
+    const bool dry = G.dry[g] != 0;
+    uint32_t chk = 0, bad = 0;
+    int64_t first = INT64_MAX;
+    const int64_t len = imin64((int64_t)plen[g], cap);
+    if (threadIdx.x == 0 && cap > 0 && (int64_t)plen[g] > cap) { ++bad; first = a; }
+    for (int64_t b = 0; b < cap; b += 256) {
+        const int64_t i = b + threadIdx.x;
+        if (i >= cap) continue;
+        const uint32_t w = g_memb[a + i];
+        bool wrong;
+        if (i >= len) {
+            wrong = w != MEMB_PAD_WORD;
+        } else {
+            const uint32_t j = w & MEMB_NODE_MASK, nib = w >> MEMB_FLAG_SHIFT;
+            if ((int64_t)j >= A.n_cap) {
+                wrong = true;
+            } else {
+                const uint32_t nf = N.flags[j];
+                if (nf & ESC_NF_ABSENT) {
+                    wrong = nib != ESC_NF_ABSENT;
+                } else {
+                    ++chk;
+                    uint32_t want = nf & 0xFu;
+                    if (dry && (want & ESC_NF_TRACKED) && !tracked(N, (int32_t)j, g)) want &= ~ESC_NF_TRACKED;
+                    wrong = nib != want || !node_has_pair(N, j, q);
+                }
+                if (i > 0) {
+                    const uint32_t pj = g_memb[a + i - 1] & MEMB_NODE_MASK;
+                    if ((int64_t)pj < A.n_cap) {
+                        const int64_t tp = N.created[pj], tj = N.created[j];
+                        wrong |= tp > tj || (tp == tj && pj > j);
+                    }
+                }
+            }
+        }
+        if (wrong) { ++bad; first = imin64(first, a + i); }
+    }
+    const uint32_t live = wave_total32(chk);
+    if ((threadIdx.x & 63) == 0 && live)
+        __hip_atomic_fetch_add(A.memb_cnt + g, live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    audit_emit(A.rep, ESC_AUD_REGION, chk, bad, first);
+}
+
+// OCC.  Thread e: both occupancy words of a live entry of a group pair (K6's own test) against
+// the recount.
+__global__ __launch_bounds__(256) void k_audit_occ(NodeDev N, GroupDev G, AuditDev A, const uint32_t* __restrict__ fresh,
+                                                   const uint32_t* __restrict__ kept) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t chk = 0, bad = 0;
+    if (e < A.n_entries && A.e_pair[e] < G.n_gp && !(N.e_flags[e] & ESC_NF_ABSENT)) {
+        chk = 1;
+        bad = (fresh[e] != kept[e] || fresh[A.n_entries + e] != kept[A.n_entries + e]) ? 1u : 0u;
+    }
+    audit_emit(A.rep, ESC_AUD_OCC, chk, bad, bad ? e : INT64_MAX);
+}
+
+// TRACKER.  Thread i as node slot i: its tracker bit is set exactly when the sorted (node,
+// group) list names it, and trk_start[i] is its first entry there (NONE: none).  Thread i as
+// list entry i: a node of the table, a group, strictly above entry i - 1.
+__global__ __launch_bounds__(256) void k_audit_tracker(NodeDev N, GroupDev G, AuditDev A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t chk = 0, bad = 0;
+    int64_t first = INT64_MAX;
+    if (i < A.n_cap) {
+        chk = 1;
+        int64_t lo = 0, hi = N.n_trk;                              // first entry with node >= i
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)N.trk_node[mid] < i) lo = mid + 1; else hi = mid;
+        }
+        const bool listed = lo < N.n_trk && (int64_t)N.trk_node[lo] == i;
+        const uint32_t f = N.flags[i];
+        const bool wrong = ((f & ESC_NF_TRACKED) != 0) != listed || N.trk_start[i] != (listed ? (uint32_t)lo : NONE) ||
+                           (listed && (f & ESC_NF_ABSENT));
+        if (wrong) { bad = 1; first = i; }
+    }
+    if (i < N.n_trk) {
+        const int64_t j = N.trk_node[i], g = N.trk_group[i];
+        bool wrong = j < 0 || j >= A.n_cap || g < 0 || g >= G.G;
+        if (i > 0) {
+            const int64_t pj = N.trk_node[i - 1], pg = N.trk_group[i - 1];
+            wrong |= pj > j || (pj == j && pg >= g);
+        }
+        if (wrong) { ++bad; first = imin64(first, j >= 0 && j < A.n_cap ? j : 0); }
+    }
+    audit_emit(A.rep, ESC_AUD_TRACKER, chk, bad, first);
+}
+
 // ===================================================================== launchers
 hipError_t launch_pod_bigtiles(const PodDev& p, const GroupDev& g, const uint32_t* tiles, int64_t n_big,
                                int64_t* wide, hipStream_t st) {
@@ -3375,6 +3592,46 @@ hipError_t launch_new_nodes(const NodeDev& n, const GroupDev& g, const NewNodesD
 hipError_t launch_node_inst(int64_t* inst_ns, const int64_t* ids, const int64_t* ev_inst, int64_t n, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_node_inst, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, inst_ns, ids, ev_inst, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_entries(const NodeDev& n, const GroupDev& g, const AuditDev& a, hipStream_t st) {
+    if (g.n_gp == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_audit_entries, dim3(g.n_gp), dim3(256), 0, st, n, g, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_node_entries(const NodeDev& n, const GroupDev& g, const AuditDev& a, hipStream_t st) {
+    if (a.n_cap <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_audit_node_entries, dim3((unsigned)((a.n_cap + 255) / 256)), dim3(256), 0, st, n, g, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_first(const NodeDev& n, const GroupDev& g, const GroupList& list, const AuditDev& a,
+                              hipStream_t st) {
+    if (list.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_audit_first, dim3(list.n), dim3(64), 0, st, n, g, list, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_regions(const NodeDev& n, const GroupDev& g, const uint32_t* pstart, const uint32_t* plen,
+                                const uint32_t* g_memb, const AuditDev& a, hipStream_t st) {
+    if (g.G <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_audit_regions, dim3(g.G), dim3(256), 0, st, n, g, pstart, plen, g_memb, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_occ(const NodeDev& n, const GroupDev& g, const AuditDev& a, const uint32_t* fresh,
+                            const uint32_t* kept, hipStream_t st) {
+    if (a.n_entries <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_audit_occ, dim3((unsigned)((a.n_entries + 255) / 256)), dim3(256), 0, st, n, g, a, fresh, kept);
+    return hipGetLastError();
+}
+
+hipError_t launch_audit_tracker(const NodeDev& n, const GroupDev& g, const AuditDev& a, hipStream_t st) {
+    const int64_t m = std::max<int64_t>(a.n_cap, n.n_trk);
+    if (m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_audit_tracker, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, n, g, a);
     return hipGetLastError();
 }
 

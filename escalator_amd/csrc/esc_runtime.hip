@@ -4784,6 +4784,293 @@ int32_t esc_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known, 
     return ESC_OK;
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------- audit
+namespace {
+
+// Device scratch of one audit, freed on every way out.
+struct AuditScratch {
+    std::vector<void*> bufs;
+    ~AuditScratch() { for (void* p : bufs) hipFree(p); }
+    template <class T>
+    hipError_t get(T** p, size_t n) {
+        const hipError_t e = dalloc(p, n);
+        if (e == hipSuccess) bufs.push_back(*p);
+        return e;
+    }
+};
+
+void audit_bad(esc_audit_check& k, int64_t id) {
+    ++k.n_bad;
+    if (k.first_bad < 0 || id < k.first_bad) k.first_bad = id;
+}
+
+// TOUCH on the host (the tables are small): every column the recount `fresh` finds touched is
+// in the maintained bitmap h_touch, every workgroup's device list holds exactly its bitmap row's
+// columns, and the destinations are the columns' ranges handed out in workgroup order — what
+// touch_upload derives from the bitmap.  An offender is a (workgroup, column) pair, counted once.
+void audit_touch(const esc_ctx* c, const std::vector<uint32_t>& fresh, const std::vector<uint2>& cols,
+                 const std::vector<uint32_t>& wg_off, const std::vector<uint32_t>& col_rows, esc_audit_check& k) {
+    const int64_t nblk = c->nblk, tw = c->touch_tw, n_col = slot_stride(c) / FC_COL;
+    std::vector<uint64_t> bad;
+    auto key = [](int64_t b, int64_t col) { return ((uint64_t)b << 32) | (uint64_t)(uint32_t)col; };
+    auto kept = [&](int64_t b, int64_t col) { return (c->h_touch[b * tw + (col >> 5)] >> (col & 31)) & 1u; };
+    std::vector<uint32_t> seen(n_col, 0), stamp(n_col, 0);
+    for (int64_t b = 0; b < nblk; ++b) {
+        for (int64_t w = 0; w < tw; ++w)
+            for (uint32_t x = fresh[b * tw + w]; x; x &= x - 1) {
+                const int64_t col = w * 32 + __builtin_ctz(x);
+                if (col >= n_col) continue;
+                ++k.n_checked;
+                if (!kept(b, col)) bad.push_back(key(b, col));
+            }
+        const int64_t cnt = std::min<int64_t>(wg_off[b], n_col);
+        if ((int64_t)wg_off[b] > n_col) bad.push_back(key(b, 0xFFFFFFFFll));
+        for (int64_t i = 0; i < cnt; ++i) {
+            const uint2 e = cols[b * n_col + i];
+            if ((int64_t)e.x >= n_col) { bad.push_back(key(b, e.x)); continue; }
+            if (stamp[e.x] == (uint32_t)b + 1 || !kept(b, e.x) || e.y != col_rows[e.x] + seen[e.x]) bad.push_back(key(b, e.x));
+            if (stamp[e.x] != (uint32_t)b + 1) ++seen[e.x];
+            stamp[e.x] = (uint32_t)b + 1;
+        }
+        for (int64_t w = 0; w < tw; ++w)
+            for (uint32_t x = c->h_touch[b * tw + w]; x; x &= x - 1) {
+                const int64_t col = w * 32 + __builtin_ctz(x);
+                if (col < n_col && stamp[col] != (uint32_t)b + 1) bad.push_back(key(b, col));
+            }
+    }
+    for (int64_t col = 0; col < n_col; ++col)                  // the columns' ranges (K3 reads them)
+        if (col_rows[col + 1] - col_rows[col] != seen[col] || (col == 0 && col_rows[0] != 0)) bad.push_back(key(nblk, col));
+    std::sort(bad.begin(), bad.end());
+    bad.erase(std::unique(bad.begin(), bad.end()), bad.end());
+    for (uint64_t x : bad) audit_bad(k, (int64_t)x);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t esc_audit(esc_ctx* c, uint32_t checks, esc_audit_report* out) {
+    if (c && c->multi) return esc::multi_audit(c, checks, out);
+    if (!c || !out || (checks >> ESC_AUD_N)) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
+    if (!checks) checks = (1u << ESC_AUD_N) - 1;
+    std::memset(out, 0, sizeof *out);
+    for (esc_audit_check& k : out->check) k.first_bad = -1;
+    // a check whose derived state is not resident is skipped: the occupancy words come with a
+    // placement, the regions with a valid age index, the touch tables with the first step's
+    // static K1 plan
+    uint32_t skip = 0;
+    if (!c->placed || !c->d_e_pair || !c->d_occ) skip |= 1u << ESC_AUD_OCC;
+    if (!(c->age_built && c->age_ok && !c->h_pcap.empty() && c->d_g_memb)) skip |= 1u << ESC_AUD_REGION;
+    if (!c->pods_loaded || !c->work_ready || !c->touch_on || !c->d_k1seg || c->pods.empty()) skip |= 1u << ESC_AUD_TOUCH;
+    out->skipped = checks & skip;
+    out->ran = checks & ~skip;
+    const uint32_t run = out->ran;
+    auto on = [&](int k) { return (run >> k) & 1u; };
+    hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    const GroupDev g = group_dev(c);
+    const NodeDev n = node_dev(c);
+    const int32_t G = c->gi.G;
+    const uint32_t n_gp = c->gi.n_gp;
+    const int64_t E = c->n_entries, NC = c->n_cap;
+    AuditScratch S;
+    AuditDev a{};
+    std::vector<int64_t> rep((size_t)ESC_AUD_N * AW_K, 0);
+    for (int k = 0; k < ESC_AUD_N; ++k) rep[(size_t)k * AW_K + AW_FIRST] = INT64_MAX;
+    HIP_TRY(S.get(&a.rep, rep.size()));
+    HIP_TRY(hipMemcpyAsync(a.rep, rep.data(), rep.size() * 8, hipMemcpyHostToDevice, st));
+    a.n_cap = NC;
+    a.n_entries = E;
+    a.e_pair = c->placed ? c->d_e_pair : nullptr;
+    std::vector<uint32_t> pair_cnt(std::max<uint32_t>(n_gp, 1), 0), memb_cnt((size_t)std::max<int32_t>(G, 1), 0);
+    std::vector<uint32_t> own;                                  // the groups whose node side this rank owns
+    for (int32_t q = 0; q < G; ++q)
+        if (owns_group(c, (uint32_t)q)) own.push_back((uint32_t)q);
+    if (on(ESC_AUD_ENTRY)) {
+        if (int32_t rc = ensure_ne_dev(c)) return rc;           // (the lazily uploaded map, re-sent when out of date)
+        a.ne_off = c->d_ne_off;
+        a.ne_pos = c->d_ne_pos;
+        a.ne_len = (int64_t)c->ne_pos.size();
+        HIP_TRY(S.get(&a.pair_cnt, pair_cnt.size()));
+        HIP_TRY(hipMemsetAsync(a.pair_cnt, 0, pair_cnt.size() * 4, st));
+        HIP_TRY(launch_audit_entries(n, g, a, st));
+        HIP_TRY(launch_audit_node_entries(n, g, a, st));
+        HIP_TRY(hipMemcpyAsync(pair_cnt.data(), a.pair_cnt, pair_cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (on(ESC_AUD_FIRST) && !own.empty()) {
+        uint32_t* d_own = nullptr;
+        HIP_TRY(S.get(&d_own, own.size()));
+        HIP_TRY(hipMemcpyAsync(d_own, own.data(), own.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_audit_first(n, g, GroupList{d_own, (int32_t)own.size(), 0}, a, st));
+    }
+    if (on(ESC_AUD_REGION) && G > 0) {
+        uint32_t *d_ps = nullptr, *d_pl = nullptr;
+        HIP_TRY(S.get(&d_ps, (size_t)G + 1));
+        HIP_TRY(S.get(&d_pl, (size_t)G));
+        HIP_TRY(S.get(&a.memb_cnt, memb_cnt.size()));
+        HIP_TRY(hipMemcpyAsync(d_ps, c->h_pstart.data(), ((size_t)G + 1) * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_pl, c->h_plen.data(), (size_t)G * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(a.memb_cnt, 0, memb_cnt.size() * 4, st));
+        HIP_TRY(launch_audit_regions(n, g, d_ps, d_pl, c->d_g_memb, a, st));
+        HIP_TRY(hipMemcpyAsync(memb_cnt.data(), a.memb_cnt, memb_cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (on(ESC_AUD_OCC) && E > 0) {
+        // K6 into scratch through a view of the placement that points there, then the compare
+        uint32_t* fresh = nullptr;
+        HIP_TRY(S.get(&fresh, (size_t)(2 * E)));
+        RemovalDev r = occ_dev(c);
+        const uint32_t* kept = r.occ_pair;
+        r.occ_pair = fresh;
+        r.occ_def = fresh + E;
+        HIP_TRY(launch_occupancy(n, g, r, st));
+        HIP_TRY(launch_audit_occ(n, g, a, fresh, kept, st));
+    }
+    std::vector<uint32_t> t_fresh, t_off, t_rows;
+    std::vector<uint2> t_cols;
+    if (on(ESC_AUD_TOUCH)) {
+        const int64_t n_col = slot_stride(c) / FC_COL;
+        t_fresh.assign((size_t)c->nblk * c->touch_tw, 0);
+        t_off.assign((size_t)c->nblk, 0);
+        t_rows.assign((size_t)n_col + 1, 0);
+        t_cols.assign((size_t)c->nblk * n_col, make_uint2(0, 0));
+        uint32_t* d_bits = nullptr;
+        HIP_TRY(S.get(&d_bits, t_fresh.size()));
+        HIP_TRY(launch_touch(pod_dev(c, 0), g, c->nblk, c->touch_tw, d_bits, st));
+        HIP_TRY(hipMemcpyAsync(t_fresh.data(), d_bits, t_fresh.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t_off.data(), c->d_wg_off, t_off.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t_rows.data(), c->d_col_rows, t_rows.size() * 4, hipMemcpyDeviceToHost, st));
+        if (!t_cols.empty())
+            HIP_TRY(hipMemcpyAsync(t_cols.data(), c->d_wg_cols, t_cols.size() * sizeof(uint2), hipMemcpyDeviceToHost, st));
+    }
+    if (on(ESC_AUD_TRACKER)) HIP_TRY(launch_audit_tracker(n, g, a, st));
+    std::vector<uint32_t> m_flags, m_label0;
+    std::vector<int64_t> m_cpu, m_mem;
+    if (on(ESC_AUD_MIRROR) && NC > 0) {
+        m_flags.resize(NC); m_label0.resize(NC); m_cpu.resize(NC); m_mem.resize(NC);
+        HIP_TRY(hipMemcpyAsync(m_flags.data(), c->nodes.flags, NC * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(m_label0.data(), c->nodes.label0, NC * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(m_cpu.data(), c->nodes.cpu, NC * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(m_mem.data(), c->nodes.mem, NC * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(rep.data(), a.rep, rep.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < ESC_AUD_N; ++k) {
+        esc_audit_check& x = out->check[k];
+        x.n_checked = rep[(size_t)k * AW_K + AW_CHECKED];
+        x.n_bad = rep[(size_t)k * AW_K + AW_BAD];
+        x.first_bad = x.n_bad ? rep[(size_t)k * AW_K + AW_FIRST] : -1;
+    }
+    if (on(ESC_AUD_ENTRY))                                      // per-pair live counts against the host's
+        for (uint32_t q = 0; q < n_gp; ++q)
+            if ((int64_t)pair_cnt[q] != c->pair_live[q]) audit_bad(out->check[ESC_AUD_ENTRY], c->pair_lo[q]);
+    if (on(ESC_AUD_REGION))                                     // a group's live memberships = its pair's live entries
+        for (uint32_t q : own)
+            if ((int64_t)memb_cnt[q] != c->pair_live[c->gi.gpair[q]]) audit_bad(out->check[ESC_AUD_REGION], c->h_pstart[q]);
+    if (on(ESC_AUD_TOUCH)) audit_touch(c, t_fresh, t_cols, t_off, t_rows, out->check[ESC_AUD_TOUCH]);
+    if (on(ESC_AUD_MIRROR)) {
+        esc_audit_check& x = out->check[ESC_AUD_MIRROR];
+        x.n_checked = NC;
+        for (int64_t j = 0; j < NC; ++j)
+            if (m_flags[j] != c->h_nflags[j] || m_cpu[j] != c->h_ncpu[j] || m_mem[j] != c->h_nmem[j] ||
+                m_label0[j] != c->h_label0[j])
+                audit_bad(x, j);
+    }
+    return ESC_OK;
+}
+
+#if ESC_MEASURE
+// Corruption injection (measurement library only; not in the header; tests/audit_child.py): one
+// derived word made wrong, so that a test can show the matching audit check sees it.  Only
+// VALUE words are reachable — no kernel uses one of them as an address, index, offset, length
+// or loop bound — so a poke changes numbers, never where a kernel reads or writes:
+//   0 entry `index`: its UNSCHED / TAINTED bits ^= value (1..3)   1 entry: e_cpu (and the packed copy) = value
+//   2 region word `index`: UNSCHED / TAINTED / TRACKED of its nibble ^= value (1..7)
+//   3 region words `index`, `index` + 1 swapped (two memberships of one group)
+//   4 occupancy word `index` of [2][n_entries] = value       5 touch bitmap: workgroup `index`, set column `value` cleared
+//   6 node `index`: ESC_NF_TRACKED flipped in the device node table only
+//   7 group `index`: GroupNode::first_cpu = value            8 node `index`: the host mirror h_ncpu = value
+// Everything else is ESC_E_INVAL.
+int32_t esc_debug_poke(esc_ctx* c, int32_t what, int64_t index, int64_t value) {
+    if (!c || c->multi || index < 0) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
+    hipSetDevice(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    auto live_entry = [&](int64_t e) {                         // an entry of a group pair whose node is live
+        return e < c->n_entries && c->h_e_node[e] != NONE && !(c->h_nflags[c->h_e_node[e]] & ESC_NF_ABSENT) &&
+               entry_pair(c, (uint32_t)e) != NONE;
+    };
+    // the owned group whose live memberships hold region word i (h_pstart / h_plen), or -1
+    auto region_group = [&](int64_t i) -> int32_t {
+        if (!(c->age_built && c->age_ok) || c->h_pstart.empty()) return -1;
+        for (int32_t q = 0; q < c->gi.G; ++q)
+            if (owns_group(c, (uint32_t)q) && i >= c->h_pstart[q] && i < (int64_t)c->h_pstart[q] + c->h_plen[q]) return q;
+        return -1;
+    };
+    uint32_t w = 0, w2 = 0;
+    switch (what) {
+    case 0:
+        if (!live_entry(index) || value < 1 || value > 3) return ESC_E_INVAL;
+        HIP_TRY(hipMemcpy(&w, c->nodes.e_flags + index, 4, hipMemcpyDeviceToHost));
+        w ^= (uint32_t)value;
+        HIP_TRY(hipMemcpy(c->nodes.e_flags + index, &w, 4, hipMemcpyHostToDevice));
+        return ESC_OK;
+    case 1:
+        if (!live_entry(index) || !entry_cpu_packs(value)) return ESC_E_INVAL;
+        w = (uint32_t)value;
+        HIP_TRY(hipMemcpy(c->nodes.e_cpu + index, &value, 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(reinterpret_cast<uint32_t*>(c->nodes.e_pk + index) + 1, &w, 4, hipMemcpyHostToDevice));
+        return ESC_OK;
+    case 2:
+        if (region_group(index) < 0 || value < 1 || value > 7) return ESC_E_INVAL;
+        HIP_TRY(hipMemcpy(&w, c->d_g_memb + index, 4, hipMemcpyDeviceToHost));
+        w ^= (uint32_t)value << MEMB_FLAG_SHIFT;
+        HIP_TRY(hipMemcpy(c->d_g_memb + index, &w, 4, hipMemcpyHostToDevice));
+        return ESC_OK;
+    case 3:
+        if (region_group(index) < 0 || region_group(index) != region_group(index + 1)) return ESC_E_INVAL;
+        HIP_TRY(hipMemcpy(&w, c->d_g_memb + index, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&w2, c->d_g_memb + index + 1, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c->d_g_memb + index, &w2, 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_g_memb + index + 1, &w, 4, hipMemcpyHostToDevice));
+        return ESC_OK;
+    case 4: {
+        uint32_t* o = c->d_occ_local ? c->d_occ_local : c->d_occ;
+        if (!c->placed || !o || index >= 2 * c->n_entries || value < 0 || value > (int64_t)0xFFFFFFFF) return ESC_E_INVAL;
+        if (!live_entry(index % c->n_entries)) return ESC_E_INVAL;   // a word K7 reads
+        w = (uint32_t)value;
+        HIP_TRY(hipMemcpy(o + index, &w, 4, hipMemcpyHostToDevice));
+        return ESC_OK;
+    }
+    case 5:
+        if (!c->touch_on || index >= c->nblk || value < 0 || value >= slot_stride(c) / FC_COL) return ESC_E_INVAL;
+        if (!((c->h_touch[(size_t)index * c->touch_tw + (size_t)(value >> 5)] >> (value & 31)) & 1u)) return ESC_E_INVAL;
+        c->h_touch[(size_t)index * c->touch_tw + (size_t)(value >> 5)] &= ~(1u << (value & 31));
+        return ESC_OK;
+    case 6:
+        if (index >= c->n_nodes || (c->h_nflags[index] & ESC_NF_ABSENT)) return ESC_E_INVAL;
+        HIP_TRY(hipMemcpy(&w, c->nodes.flags + index, 4, hipMemcpyDeviceToHost));
+        w ^= ESC_NF_TRACKED;
+        HIP_TRY(hipMemcpy(c->nodes.flags + index, &w, 4, hipMemcpyHostToDevice));
+        return ESC_OK;
+    case 7:
+        if (index >= c->gi.G) return ESC_E_INVAL;
+        HIP_TRY(hipMemcpy(&c->nodes.gnode[index].first_cpu, &value, 8, hipMemcpyHostToDevice));
+        return ESC_OK;
+    case 8:
+        if (index >= c->n_nodes || (c->h_nflags[index] & ESC_NF_ABSENT)) return ESC_E_INVAL;
+        c->h_ncpu[index] = value;
+        return ESC_OK;
+    default:
+        return ESC_E_INVAL;
+    }
+}
+#endif
+
 // ----------------------------------------------------------------- ordering
 int32_t esc_sort_nodes(esc_ctx* c) {
     if (c && c->multi) return esc::multi_each(c, [](esc_ctx* x, int32_t) { return esc_sort_nodes(x); }, 0);

@@ -81,7 +81,7 @@ class EventQueue:
         self._dirty_nodes: dict[str, bool] = {}
         self._loaded = False
         self.reloads = 0
-        self.reload_causes: list[str] = []         # "first", or the call that answered ESC_E_LIMIT
+        self.reload_causes: list[str] = []         # "first", the call that answered ESC_E_LIMIT, or "audit:<check>"
         self.flushes = 0
         self.applied = {k: 0 for k in KINDS}
         self.touched_nodes = False                 # the last flush added nodes or reloaded
@@ -185,6 +185,16 @@ class EventQueue:
         except _Reload as e:
             self.reload_causes.append(str(e))
             self._reload(ctx, dirty_p, dirty_n)
+
+    def reload(self, ctx, cause: str):
+        """One full load from the object store outside a flush (a failed audit): `cause` goes
+        into ``reload_causes``, whatever was ingested since the last flush is taken along."""
+        if not self._loaded:
+            return self.flush(ctx)
+        dirty_p, dirty_n = self._dirty_pods, self._dirty_nodes
+        self._dirty_pods, self._dirty_nodes = {}, {}
+        self.reload_causes.append(cause)
+        self._reload(ctx, dirty_p, dirty_n)
 
     def _apply(self, ctx, dirty_p, dirty_n):
         dev_n, idx = self._dev_nodes, self._node_idx

@@ -898,3 +898,46 @@ func (x *Context) NewNodeList(g int) ([]int64, []bool, error) {
 	}
 	return idx, out, nil
 }
+
+// AuditChecks names esc_audit's checks in ESC_AUD_* order.
+var AuditChecks = [C.ESC_AUD_N]string{"ENTRY", "FIRST", "REGION", "OCC", "TOUCH", "TRACKER", "MIRROR"}
+
+// AuditCheck is one check's result: FirstBad is the lowest offending id, -1 when Bad == 0.
+type AuditCheck struct {
+	Checked, Bad, FirstBad int64
+}
+
+// AuditReport is esc_audit's report: Ran and Skipped hold a bit per check (1 << ESC_AUD_*); a
+// check is skipped when its state is not resident (OCC without a placement, REGION without a
+// valid age index, TOUCH before the first decision's K1 plan).
+type AuditReport struct {
+	Ran, Skipped uint32
+	Check        [C.ESC_AUD_N]AuditCheck
+}
+
+// Clean reports whether no check that ran found a mismatch.
+func (r *AuditReport) Clean() bool {
+	for _, k := range r.Check {
+		if k.Bad != 0 {
+			return false
+		}
+	}
+	return true
+}
+
+// Audit recomputes the resident snapshot's derived state from its primary tables (every check)
+// and reports the differences — the counterpart of the informers' resync (pkg/k8s/cache.go:27,48)
+// for the state this library derives on the device.  Mismatches are data, not an error: on
+// !Clean() reload the snapshot (LoadPods, LoadNodes, the placement) and re-add the trackers.
+func (x *Context) Audit() (*AuditReport, error) {
+	var rep C.esc_audit_report
+	if rc := C.esc_audit(x.c, 0, &rep); rc != C.ESC_OK {
+		return nil, rcErr("esc_audit", rc)
+	}
+	out := &AuditReport{Ran: uint32(rep.ran), Skipped: uint32(rep.skipped)}
+	for k := range out.Check {
+		out.Check[k] = AuditCheck{Checked: int64(rep.check[k].n_checked), Bad: int64(rep.check[k].n_bad),
+			FirstBad: int64(rep.check[k].first_bad)}
+	}
+	return out, nil
+}

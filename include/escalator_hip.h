@@ -675,6 +675,54 @@ int32_t esc_new_nodes_eval(esc_ctx* ctx, const int64_t* since_unix_ns, esc_new_n
    NULL too); ESC_E_LIMIT when cap is short. */
 int32_t esc_new_nodes_list(esc_ctx* ctx, int32_t group, int64_t* idx_out, uint8_t* known_out, int64_t cap, int64_t* n_out);
 
+/* ------------------------------------------------------------------- audit
+ * The resident snapshot holds state that is derived from its primary tables and maintained in
+ * place by the event calls above.  esc_audit is a read-only pass that recomputes each derived
+ * structure from its primary one and reports the differences — the resident counterpart of
+ * the reference informers' hourly resync (pkg/k8s/cache.go:27,48):
+ *   ENTRY    every live pair-major entry of a group pair against its node (the node is live and
+ *            carries the pair; class bits, allocatable and the packed record are the node
+ *            table's); every live node's group pairs each map to exactly one live entry of the
+ *            node; per-pair live counts equal the host's.  first_bad: entry index.
+ *   FIRST    every group's cached allNodes[0] and its allocatable.  first_bad: group.
+ *   REGION   the K5 regions this rank holds: nodes, flag nibbles, (creation, node) order,
+ *            padding, live memberships per group.  first_bad: index into the regions.
+ *   OCC      a recount of the reaping occupancy words into scratch against the maintained
+ *            ones (this rank's own words with several ranks).  first_bad: entry index.
+ *   TOUCH    the compact-flush columns: every column a recount finds touched is in the
+ *            maintained bitmap, and the device's per-workgroup lists and per-column ranges are
+ *            the bitmap's.  first_bad: workgroup << 32 | column.
+ *   TRACKER  ESC_NF_TRACKED of every node against the sorted tracker list and its per-node
+ *            index.  first_bad: node.
+ *   MIRROR   the device node table against the host mirrors the event calls plan from.
+ *            first_bad: node.
+ * checks: a bit per check (1u << ESC_AUD_*), 0 = all.  A check whose state is not resident —
+ * OCC without a placement, REGION without a valid age index, TOUCH without a static K1 plan —
+ * is reported in `skipped` and left out of `ran`.  Mismatches are data: ESC_OK whenever the
+ * pass ran; ESC_E_STATE before esc_load_nodes or on a stale context; ESC_E_NODEV without a
+ * device.  Runs on the context's stream after whatever is pending and waits once at its end;
+ * it writes only its own scratch (and refreshes the lazily uploaded node -> entries map):
+ * captured steps, selections, reaping and new-node results stay as they were.  The report is
+ * deterministic (counts are sums, first_bad a minimum).  A multi-device context audits every
+ * device: counts summed, first_bad the minimum, skipped OR-ed, ran AND-ed. */
+#define ESC_AUD_ENTRY   0            /* (macros like every constant here: a debug build of the   */
+#define ESC_AUD_FIRST   1            /*  library carries no ESC_* names, tests/test_abi.py)      */
+#define ESC_AUD_REGION  2
+#define ESC_AUD_OCC     3
+#define ESC_AUD_TOUCH   4
+#define ESC_AUD_TRACKER 5
+#define ESC_AUD_MIRROR  6
+#define ESC_AUD_N       7
+typedef struct esc_audit_check {
+    int64_t n_checked, n_bad;
+    int64_t first_bad;               /* lowest offending id, -1 if none */
+} esc_audit_check;
+typedef struct esc_audit_report {
+    uint32_t ran, skipped;           /* bit per check */
+    esc_audit_check check[ESC_AUD_N];
+} esc_audit_report;
+int32_t esc_audit(esc_ctx* ctx, uint32_t checks, esc_audit_report* out);
+
 /* ----------------------------------------------------------------- ordering
  * K5: per-group creation-time order of the context's node shard (a18/a19):
  *   which 0: untainted members oldest-first (taintOldestN,   scale_down.go:171)
