@@ -314,6 +314,22 @@ class Context:
                 "esc_nodes_relabel")
         del keep
 
+    def nodes_rebuild(self):
+        """The node half of a re-list (esc_nodes_rebuild): the pair-major entries, the node ->
+        entries map, allNodes[0], the list offsets, the tracker index, the occupancy words and
+        the age index re-derived on the device from the resident node table, with fresh spare
+        room.  Node indices, pods, the K1 plan, the placement, the trackers and the
+        instantiation times stay.  The answer to nodes_add / nodes_relabel's ESC_E_LIMIT while
+        ``nodes_room()`` shows free table slots."""
+        L.check(self.lib.esc_nodes_rebuild(self.handle), "esc_nodes_rebuild")
+
+    def nodes_room(self) -> tuple[int, int]:
+        """(free node-table slots, free extra-label words): a rebuild does not grow the table,
+        so an add of more nodes than the free slots still needs a full load."""
+        a, b = C.c_int64(), C.c_int64()
+        L.check(self.lib.esc_nodes_room(self.handle, C.byref(a), C.byref(b)), "esc_nodes_room")
+        return a.value, b.value
+
     def nodes_delete(self, ids):
         """Node informer Delete events: the nodes' slots become absent."""
         ids = np.ascontiguousarray(ids, np.int64)

@@ -458,15 +458,25 @@ class ResidentController(Controller):
     ``audit_every=k`` (0 = never): on every k-th scan, after the flush and before the decision,
     ``ctx.audit()`` checks the snapshot's derived state against its primary tables; a mismatch
     reloads the snapshot once from the queue's object store (``events.reload_causes`` gets
-    ``"audit:<check>"``) and counts in ``audit_failures``; ``audits`` counts the passes."""
+    ``"audit:<check>"``) and counts in ``audit_failures``; ``audits`` counts the passes.
+
+    ``node_rebuild=True``: a ``nodes_add`` / ``nodes_relabel`` that runs out of node-side spare
+    room is answered by ``ctx.nodes_rebuild()`` and one retry before any reload
+    (``events.rebuild_causes``), and so is an audit mismatch confined to the state a rebuild
+    re-derives (ENTRY, FIRST, REGION, OCC, TRACKER): those checks are run again after it, and
+    only a mismatch that survives — or one in TOUCH or MIRROR — reloads.  The trackers outlive
+    a rebuild, so nothing is re-added after one."""
+
+    REBUILT_CHECKS = ("ENTRY", "FIRST", "REGION", "OCC", "TRACKER")
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
-                 selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0):
+                 selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0, node_rebuild: bool = False):
         super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
                          selection_slack=selection_slack)
         from .events import EventQueue
         self.spare = float(spare)
-        self.events = EventQueue(spare=self.spare)
+        self.node_rebuild = bool(node_rebuild)
+        self.events = EventQueue(spare=self.spare, rebuild=self.node_rebuild)
         # the resync of the derived state (the reference's informers resync hourly,
         # pkg/k8s/cache.go:27,48): every audit_every-th scan audits the snapshot after the flush
         # and reloads it once when a check finds a mismatch; 0 = never
@@ -501,6 +511,12 @@ class ResidentController(Controller):
         bad = [n for n in L.AUDIT_CHECKS if n in rep and rep[n]["n_bad"] > 0]
         if bad:
             self.audit_failures += 1
+            if getattr(self, "node_rebuild", False) and all(n in self.REBUILT_CHECKS for n in bad):
+                self.events.node_rebuild(self.ctx, "audit:" + bad[0])
+                again = self.ctx.audit(list(self.REBUILT_CHECKS))
+                bad = [n for n in self.REBUILT_CHECKS if n in again and again[n]["n_bad"] > 0]
+                if not bad:
+                    return
             self.events.reload(self.ctx, "audit:" + bad[0])
 
     def run_once(self) -> list[dict]:

@@ -671,6 +671,41 @@ hipError_t launch_age_sort(const NodeDev& nd, const GroupDev& g, uint64_t* statu
                            int64_t cap, int64_t ts_min, uint64_t div, int R, int gbits, int coarse_shift,
                            uint64_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* tot, const RegionSink& S,
                            hipStream_t st);
+// esc_nodes_rebuild: the pair-major entries, the node -> entries map and the compacted extra
+// labels re-derived from the resident node table.  The HOST fixes the layout from its counts
+// (every pointer marked "layout" below is host-made and uploaded); the device supplies the
+// values.  k_entry_fill writes every entry of every piece as a spare one, k_pair_list lists
+// one (pair << 32 | node) element per label of every live node at ne_off[node] + j, the
+// k_rs_* passes sort the elements by pair alone (stable: nodes stay ascending inside a pair),
+// k_entry_place puts sorted element k at its entry.  No kernel waits on another workgroup.
+// A pair, node, count or offset that does not fit the layout sets *err and indexes nothing.
+struct RebuildDev {
+    // the resident node table (read; `flags` also gets its tracker bit set from trk_start)
+    uint32_t* flags;
+    const uint32_t *label0, *xl_off, *xl;
+    const int64_t *cpu, *mem;
+    int64_t n_cap, xl_len;                 // table slots; words of xl
+    // layout
+    const uint32_t* ne_off;                // [n_cap + 1] node -> first element / map slot
+    const uint32_t* xl_off_new;            // [n_cap] node -> first word of xl_new
+    const uint32_t* trk_start;             // [n_cap] the tracker list's first entry per node
+    const uint32_t* start;                 // [n_gp + 1] group pair -> first sorted element
+    const uint32_t* pair_lo;               // [n_gp] group pair -> first entry
+    const uint32_t *piece_off, *piece_pair;
+    int64_t n_pieces, n_elems, n_entries, xl_new_cap;
+    uint32_t n_gp, spare_total;            // spare entries of all group pairs (ids >= n_gp sit behind them)
+    // built
+    uint32_t* xl_new;
+    uint32_t *e_flags, *e_node, *e_pair;   // e_pair: null without a placement
+    int64_t *e_cpu, *e_mem;
+    uint4* e_pk;
+    uint32_t* ne_pos;                      // [n_elems]
+    uint32_t* err;
+};
+// elems[2]: n_elems 8-B elements each; hist: sort_hist_words(n_elems); tot: 256 words;
+// pair_bits: bits of the largest resident pair id (one 8-bit pass per started byte).
+hipError_t launch_nodes_rebuild(const RebuildDev& r, uint64_t* elems[2], uint32_t* hist, uint32_t* tot, int pair_bits,
+                                hipStream_t st);
 // The bounded waits of the decoupled look-backs (k_ord_split, k_memb_keys): HIP does not
 // promise dispatch order, so a chunk never waits unboundedly on one that was not dispatched.
 // A chunk that waited `spins` probes gives up: it publishes a FAILED status word (never an

@@ -3475,6 +3475,112 @@ __global__ __launch_bounds__(256) void k_audit_tracker(NodeDev N, GroupDev G, Au
     audit_emit(A.rep, ESC_AUD_TRACKER, chk, bad, first);
 }
 
+// ===================================================================== node-side rebuild
+// esc_nodes_rebuild (RebuildDev, esc_kernels.h).  Every offset is the host's, so no kernel
+// here looks back at, takes a ticket from or waits for another workgroup; the sort between
+// the listing and the placing is the K5 index build's (k_rs_hist / k_rs_scan_rows /
+// k_rs_scatter on the pair bits of 8-B elements).
+namespace {
+constexpr uint32_t RB_ERR_COUNT = 1u, RB_ERR_LABEL = 2u, RB_ERR_ELEM = 4u, RB_ERR_NODE = 8u;
+__device__ __forceinline__ void rb_fail(uint32_t* err, uint32_t bit) {
+    __hip_atomic_fetch_or(err, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+}  // namespace
+
+// One workgroup per piece: every entry of the new layout starts as a spare one (absent, no
+// node) of its piece's pair; k_entry_place overwrites the live ones.
+__global__ __launch_bounds__(PIECE_ALIGN) void k_entry_fill(RebuildDev R) {
+    const int64_t p = blockIdx.x;
+    const int64_t e = (int64_t)R.piece_off[p] + threadIdx.x;
+    if (e >= (int64_t)R.piece_off[p + 1] || e >= R.n_entries) return;
+    R.e_flags[e] = ESC_NF_ABSENT;
+    R.e_node[e] = NONE;
+    R.e_cpu[e] = 0;
+    R.e_mem[e] = 0;
+    R.e_pk[e] = make_uint4(ESC_NF_ABSENT, 0u, 0u, 0u);
+    if (R.e_pair) R.e_pair[e] = R.piece_pair[p];
+}
+
+// One thread per table slot, flags / label0 / xl_off streamed coalesced: the slot's tracker
+// bit from the tracker list, its extra labels copied to their compacted place, and one
+// element per label at the host's offset.  A node whose label count is not the one the host
+// laid out, or whose labels are not ascending pair ids, lists nothing.
+__global__ __launch_bounds__(256) void k_pair_list(RebuildDev R, uint64_t* __restrict__ elems) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= R.n_cap) return;
+    uint32_t f = R.flags[i];
+    const uint32_t l0 = R.label0[i], xo = R.xl_off[i];
+    const uint32_t a = R.ne_off[i], z = R.ne_off[i + 1];
+    const uint32_t tf = (f & ~ESC_NF_TRACKED) | (R.trk_start[i] != NONE && !(f & ESC_NF_ABSENT) ? ESC_NF_TRACKED : 0u);
+    if (tf != f) R.flags[i] = f = tf;
+    const uint32_t want = (f & ESC_NF_ABSENT) || l0 == NONE ? 0u : 1u + nf_xlbl(f);
+    if (z < a || z - a != want || (int64_t)z > R.n_elems) { rb_fail(R.err, RB_ERR_COUNT); return; }
+    if (!want) return;
+    const uint32_t nx = want - 1, xn = R.xl_off_new[i];
+    if (l0 >= ESC_PAIR_LIMIT || (int64_t)xo + nx > R.xl_len || (int64_t)xn + nx > R.xl_new_cap) {
+        rb_fail(R.err, RB_ERR_LABEL);
+        return;
+    }
+    uint32_t last = l0;
+    for (uint32_t k = 0; k < nx; ++k) {
+        const uint32_t q = R.xl[xo + k];
+        if (q <= last || q >= ESC_PAIR_LIMIT) { rb_fail(R.err, RB_ERR_LABEL); return; }
+        last = q;
+    }
+    elems[a] = ((uint64_t)l0 << 32) | (uint64_t)i;
+    for (uint32_t k = 0; k < nx; ++k) {
+        const uint32_t q = R.xl[xo + k];
+        R.xl_new[xn + k] = q;
+        elems[a + 1 + k] = ((uint64_t)q << 32) | (uint64_t)i;
+    }
+}
+
+// One sorted element per thread: element k of group pair q is the pair's (k - start[q])-th
+// live entry, an element of a pair no group selects sits behind every group pair's entries
+// and spare room.  The node's class bits and allocatable are gathered into the five entry
+// arrays, and the entry goes into the node's map slot j, its label's place in the node's own
+// ascending labels.
+__global__ __launch_bounds__(256) void k_entry_place(RebuildDev R, const uint64_t* __restrict__ elems) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= R.n_elems) return;
+    const uint64_t el = elems[k];
+    const uint32_t q = (uint32_t)(el >> 32), j = (uint32_t)el;
+    if ((int64_t)j >= R.n_cap || q >= ESC_PAIR_LIMIT) { rb_fail(R.err, RB_ERR_ELEM); return; }
+    int64_t e;
+    if (q < R.n_gp) {
+        const int64_t s = R.start[q];
+        if (k < s || k >= (int64_t)R.start[q + 1]) { rb_fail(R.err, RB_ERR_ELEM); return; }
+        e = (int64_t)R.pair_lo[q] + (k - s);
+    } else {
+        if (k < (int64_t)R.start[R.n_gp]) { rb_fail(R.err, RB_ERR_ELEM); return; }
+        e = k + (int64_t)R.spare_total;
+    }
+    if (e >= R.n_entries) { rb_fail(R.err, RB_ERR_ELEM); return; }
+    const uint32_t f = R.flags[j], a = R.ne_off[j], cnt = R.ne_off[j + 1] - a;
+    if ((f & ESC_NF_ABSENT) || cnt == 0 || cnt != 1u + nf_xlbl(f) || (int64_t)a + cnt > R.n_elems) {
+        rb_fail(R.err, RB_ERR_NODE);
+        return;
+    }
+    uint32_t slot = NONE;
+    if (R.label0[j] == q) {
+        slot = 0;
+    } else {
+        const uint32_t xn = R.xl_off_new[j];
+        if ((int64_t)xn + (cnt - 1) > R.xl_new_cap) { rb_fail(R.err, RB_ERR_NODE); return; }
+        for (uint32_t t = 0; t + 1 < cnt; ++t)
+            if (R.xl_new[xn + t] == q) slot = t + 1;
+    }
+    if (slot == NONE) { rb_fail(R.err, RB_ERR_NODE); return; }
+    const int64_t cpu = R.cpu[j], mem = R.mem[j];
+    R.e_flags[e] = f;
+    R.e_node[e] = j;
+    R.e_cpu[e] = cpu;
+    R.e_mem[e] = mem;
+    R.e_pk[e] = make_uint4(f, (uint32_t)cpu, (uint32_t)(uint64_t)mem, (uint32_t)((uint64_t)mem >> 32));
+    if (R.e_pair) R.e_pair[e] = q;
+    R.ne_pos[a + slot] = (uint32_t)e;
+}
+
 // ===================================================================== launchers
 hipError_t launch_pod_bigtiles(const PodDev& p, const GroupDev& g, const uint32_t* tiles, int64_t n_big,
                                int64_t* wide, hipStream_t st) {
@@ -3738,6 +3844,28 @@ hipError_t launch_age_sort(const NodeDev& nd, const GroupDev& g, uint64_t* statu
             hipLaunchKernelGGL(k_age_fix, dim3((unsigned)std::min<int64_t>(4096, (n_memb + 1023) / 1024)), dim3(256), 0, st,
                                reinterpret_cast<const uint32_t*>(keys[src]), n_memb, S, nd.created, nd.hi, ts_min);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_nodes_rebuild(const RebuildDev& r, uint64_t* elems[2], uint32_t* hist, uint32_t* tot, int pair_bits,
+                                hipStream_t st) {
+    if (r.n_pieces > 0)
+        hipLaunchKernelGGL(k_entry_fill, dim3((unsigned)r.n_pieces), dim3(PIECE_ALIGN), 0, st, r);
+    if (r.n_cap > 0)
+        hipLaunchKernelGGL(k_pair_list, dim3((unsigned)((r.n_cap + 255) / 256)), dim3(256), 0, st, r, elems[0]);
+    if (r.n_elems <= 0) return hipGetLastError();
+    // stable LSD passes over the pair (bits 32 and up of an element), 8 bits each; the node
+    // order inside a pair is the listing's
+    int src = 0;
+    NoVal* nv = nullptr;
+    const RegionSink none{};
+    for (int b = 0; b < std::max(pair_bits, 1); b += 8) {
+        const hipError_t e = rs_pass<uint64_t, NoVal, 8>(elems[src], nv, elems[src ^ 1], nv, r.n_elems, 32 + b, hist, tot,
+                                                         none, st);
+        if (e != hipSuccess) return e;
+        src ^= 1;
+    }
+    hipLaunchKernelGGL(k_entry_place, dim3((unsigned)((r.n_elems + 255) / 256)), dim3(256), 0, st, r, elems[src]);
     return hipGetLastError();
 }
 

@@ -70,6 +70,7 @@ int32_t multi_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known
 int32_t multi_audit(esc_ctx* c, uint32_t checks, esc_audit_report* out);              // every device, merged
 int32_t multi_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out);
 int32_t multi_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n);
+int32_t multi_nodes_rebuild(esc_ctx* c);                                          // every device's node side (esc_nodes_rebuild)
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s);
 int32_t multi_tracker_update(esc_ctx* c, int32_t group, const int64_t* add, int64_t n_add, const int64_t* rm,
                              int64_t n_rm);

@@ -519,6 +519,13 @@ int32_t multi_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n) {
     return node_event(c, [&](int i) { return esc_nodes_delete(M(c).subs[i], ids, n); });
 }
 
+// Every device re-derives its own node side (esc_nodes_rebuild): no exchange.  A failure on a
+// device after another has swapped leaves the devices' node sides out of step, as a node event
+// that failed half-way does.
+int32_t multi_nodes_rebuild(esc_ctx* c) {
+    return node_event(c, [&](int i) { return esc_nodes_rebuild(M(c).subs[i]); });
+}
+
 int32_t multi_tracker_update(esc_ctx* c, int32_t group, const int64_t* add, int64_t n_add, const int64_t* rm,
                              int64_t n_rm) {
     return node_event(c, [&](int i) { return esc_tracker_update(M(c).subs[i], group, add, n_add, rm, n_rm); });

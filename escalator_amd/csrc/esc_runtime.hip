@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <new>
 #include <thread>
 #include <type_traits>
@@ -4783,6 +4784,333 @@ int32_t esc_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known, 
     }
     return ESC_OK;
 }
+
+}  // extern "C"
+
+// ------------------------------------------------ node-side rebuild
+namespace {
+
+// The buffers a rebuild builds beside the resident ones.  The swap exchanges them with the
+// context's, so whatever this holds when it goes out of scope — the new buffers of a rebuild
+// that failed, the old ones of one that succeeded, the scratch of both — is released.
+struct RebuildBufs {
+    NodeBuf nb;                                   // entries, pieces, spans, rows, gnode, xl, xl_off, trk_start
+    uint32_t *ne_off = nullptr, *ne_pos = nullptr, *e_pair = nullptr, *occ = nullptr, *occ_local = nullptr;
+    uint32_t *nn_off = nullptr, *nn_list = nullptr, *rm_off = nullptr, *rm_list = nullptr;
+    uint8_t* blob = nullptr;                      // the staged layout tables
+    uint64_t* elems[2] = {nullptr, nullptr};
+    uint32_t *hist = nullptr, *tot = nullptr;
+    ~RebuildBufs() {
+        nb.release();
+        dfree(ne_off); dfree(ne_pos); dfree(e_pair); dfree(occ); dfree(occ_local);
+        dfree(nn_off); dfree(nn_list); dfree(rm_off); dfree(rm_list);
+        dfree(blob); dfree(elems[0]); dfree(elems[1]); dfree(hist); dfree(tot);
+    }
+};
+
+// Seconds since the first call (the probe's split of a rebuild, esc_debug_rebuild_times).
+double rebuild_clock() {
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+}
+thread_local double g_rebuild_ms[6];              // host layout, upload, kernels, mirrors, occupancy, age index
+
+int32_t nodes_rebuild_one(esc_ctx* c) {
+    const uint32_t n_gp = c->gi.n_gp;
+    const int32_t G = c->gi.G;
+    const int64_t N = c->n_nodes, NC = c->n_cap;
+    const double sf = c->spare_frac;
+    if ((int64_t)c->h_nflags.size() < NC || (int64_t)c->pair_live.size() != (int64_t)n_gp) return ESC_E_STATE;
+    hipSetDevice(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    double t0 = rebuild_clock();
+    for (double& x : g_rebuild_ms) x = 0;
+    // ---- the layout, from the host's counts alone
+    // the tracker index and bit first: the entries carry the bit
+    std::vector<uint32_t> trk_start((size_t)std::max<int64_t>(NC, 1), NONE);
+    for (int64_t k = (int64_t)c->h_trk.size() - 1; k >= 0; --k) {
+        const uint64_t j = c->h_trk[k] >> 32;
+        if ((int64_t)j >= N) return fail_hip(hipErrorUnknown, "nodes rebuild: tracker mirror");
+        trk_start[j] = (uint32_t)k;
+    }
+    std::vector<uint32_t> nflags(c->h_nflags.begin(), c->h_nflags.begin() + NC);
+    std::vector<uint32_t> ne_off((size_t)NC + 1, 0), xl_off((size_t)std::max<int64_t>(NC, 1), 0);
+    uint64_t m = 0, xw = 0;
+    uint32_t max_pair = 0;
+    bool pk_ok = true;
+    for (int64_t i = 0; i < NC; ++i) {
+        ne_off[i] = (uint32_t)m;
+        xl_off[i] = (uint32_t)xw;
+        uint32_t& f = nflags[i];
+        if (i >= N || (f & ESC_NF_ABSENT)) continue;
+        f = (f & ~ESC_NF_TRACKED) | (trk_start[i] != NONE ? ESC_NF_TRACKED : 0u);
+        pk_ok = pk_ok && entry_cpu_packs(c->h_ncpu[i]);
+        if (c->h_label0[i] == NONE) continue;
+        const uint32_t nx = nf_xlbl(f);
+        if ((uint64_t)c->h_xl_off[i] + nx > c->h_xl.size()) return fail_hip(hipErrorUnknown, "nodes rebuild: label mirror");
+        max_pair = std::max(max_pair, nx ? c->h_xl[c->h_xl_off[i] + nx - 1] : c->h_label0[i]);
+        m += 1 + nx;
+        xw += nx;
+        if (m >= 0xFFFFFFFFull) return ESC_E_LIMIT;
+    }
+    ne_off[NC] = (uint32_t)m;
+    const int64_t M = (int64_t)m;
+    // the extra labels, compacted to the live nodes' words
+    std::vector<uint32_t> h_xl((size_t)xw);
+    for (int64_t i = 0; i < N; ++i) {
+        if ((nflags[i] & ESC_NF_ABSENT) || c->h_label0[i] == NONE) continue;
+        const uint32_t nx = nf_xlbl(nflags[i]);
+        std::copy_n(c->h_xl.begin() + c->h_xl_off[i], nx, h_xl.begin() + xl_off[i]);
+    }
+    const int64_t xl_cap = (int64_t)xw + (sf > 0 ? (int64_t)std::ceil((double)xw * sf) + 256 : 0);
+    // group pairs: live entries sorted by node, then ceil(live * f) + 4 spare ones; the
+    // entries of pairs no group selects follow all of them
+    std::vector<uint32_t> start((size_t)n_gp + 1), pair_lo(n_gp), pair_next(n_gp), pair_end(n_gp);
+    uint64_t s_acc = 0, e_acc = 0;
+    for (uint32_t q = 0; q < n_gp; ++q) {
+        const int64_t live = c->pair_live[q];
+        if (live < 0) return fail_hip(hipErrorUnknown, "nodes rebuild: pair mirror");
+        const int64_t sp = sf > 0 ? (int64_t)std::ceil((double)live * sf) + 4 : 0;
+        start[q] = (uint32_t)s_acc;
+        pair_lo[q] = (uint32_t)e_acc;
+        s_acc += (uint64_t)live;
+        e_acc += (uint64_t)(live + sp);
+        if (e_acc >= 0xFFFFFFFFull) return ESC_E_LIMIT;
+        pair_next[q] = pair_lo[q] + (uint32_t)live;
+        pair_end[q] = (uint32_t)e_acc;
+    }
+    start[n_gp] = (uint32_t)s_acc;
+    if ((int64_t)s_acc > M) return fail_hip(hipErrorUnknown, "nodes rebuild: pair mirror");
+    const uint64_t spare_total = e_acc - s_acc;
+    const int64_t E = M + (int64_t)spare_total;
+    if (E >= (int64_t)0xFFFFFFFF) return ESC_E_LIMIT;
+    // pieces: runs of one pair that cross no multiple of PIECE_ALIGN (as esc_load_nodes cuts
+    // them); the entries behind the group pairs are cut at the alignment alone (pair NONE:
+    // nothing reads a piece of a pair no group selects)
+    std::vector<uint32_t> piece_off, piece_pair, pp_off((size_t)n_gp + 1);
+    auto cut = [&](uint64_t a, uint64_t z, uint32_t q) {
+        while (a < z) {
+            piece_off.push_back((uint32_t)a);
+            piece_pair.push_back(q);
+            a = std::min<uint64_t>(z, (a / PIECE_ALIGN + 1) * PIECE_ALIGN);
+        }
+    };
+    for (uint32_t q = 0; q < n_gp; ++q) {
+        pp_off[q] = (uint32_t)piece_pair.size();
+        cut(pair_lo[q], pair_end[q], q);
+    }
+    pp_off[n_gp] = (uint32_t)piece_pair.size();
+    cut(e_acc, (uint64_t)E, NONE);
+    const int64_t n_pieces = (int64_t)piece_pair.size();
+    piece_off.push_back((uint32_t)E);
+    // this rank's share inside the kept owner bounds, K2's bytes and spans (as esc_load_nodes)
+    const int64_t pc_lo = pp_off[c->q_lo], pc_hi = pp_off[c->q_hi];
+    const int64_t per_entry = pk_ok ? 16 : 20;
+    int64_t node_bytes = 0;
+    for (int64_t p = pc_lo; p < pc_hi; ++p) node_bytes += 8 + per_entry * (int64_t)(piece_off[p + 1] - piece_off[p]);
+    std::vector<uint32_t> span_off(1, (uint32_t)pc_lo);
+    {
+        int64_t acc = 0, np = 0;
+        for (int64_t p = pc_lo; p < pc_hi; ++p) {
+            const int64_t len = (int64_t)piece_off[p + 1] - piece_off[p];
+            if (acc > 0 && (acc + len > NODE_SPAN || np == 63)) { span_off.push_back((uint32_t)p); acc = 0; np = 0; }
+            acc += len;
+            ++np;
+        }
+        if (pc_hi > pc_lo) span_off.push_back((uint32_t)pc_hi);
+    }
+    std::vector<uint32_t> span_e(span_off.size());
+    for (size_t w = 0; w < span_off.size(); ++w) span_e[w] = piece_off[span_off[w]];
+    // a group's new-node and removal lists hold at most its pair's entry capacity
+    std::vector<uint32_t> list_off((size_t)G + 1, 0);
+    for (int32_t g = 0; g < G; ++g) {
+        const uint32_t q = c->gi.gpair[g];
+        const uint64_t end = (uint64_t)list_off[g] + (pair_end[q] - pair_lo[q]);
+        if (end >= 0xFFFFFFFFull) return ESC_E_LIMIT;
+        list_off[g + 1] = (uint32_t)end;
+    }
+    // ---- one staged copy of every table (the error word, zero, at its end)
+    struct Part { const std::vector<uint32_t>* v; size_t at; };
+    Part parts[] = {{&ne_off, 0}, {&xl_off, 0}, {&trk_start, 0}, {&start, 0}, {&pair_lo, 0}, {&piece_off, 0},
+                    {&piece_pair, 0}, {&pp_off, 0}, {&span_off, 0}, {&span_e, 0}, {&list_off, 0}};
+    enum { P_NE, P_XLO, P_TRK, P_START, P_LO, P_POFF, P_PPAIR, P_PP, P_SOFF, P_SE, P_LIST, P_N };
+    size_t bytes = 0;
+    for (Part& p : parts) { p.at = bytes; bytes += (p.v->size() * 4 + 255) & ~(size_t)255; }
+    const size_t err_at = bytes;
+    bytes += 256;
+    std::vector<uint8_t> stage(bytes, 0);
+    for (const Part& p : parts)
+        if (!p.v->empty()) std::memcpy(stage.data() + p.at, p.v->data(), p.v->size() * 4);
+    g_rebuild_ms[0] = (rebuild_clock() - t0) * 1e3;
+    t0 = rebuild_clock();
+    // ---- the new buffers, beside the resident ones
+    RebuildBufs B;
+    NodeBuf& b = B.nb;
+    const size_t Ez = (size_t)std::max<int64_t>(E, 1), Pz = (size_t)std::max<int64_t>(n_pieces, 1);
+    const bool reap = c->d_e_pair != nullptr;     // esc_load_placement's per-entry buffers exist
+    HIP_TRY(dalloc(&B.blob, bytes));
+    HIP_TRY(dalloc(&b.e_flags, Ez)); HIP_TRY(dalloc(&b.e_node, Ez)); HIP_TRY(dalloc(&b.e_cpu, Ez));
+    HIP_TRY(dalloc(&b.e_mem, Ez)); HIP_TRY(dalloc(&b.e_pk, Ez));
+    HIP_TRY(dalloc(&b.piece_off, piece_off.size())); HIP_TRY(dalloc(&b.piece_pair, Pz));
+    HIP_TRY(dalloc(&b.pp_off, pp_off.size())); HIP_TRY(dalloc(&b.span_off, span_off.size()));
+    HIP_TRY(dalloc(&b.span_e, span_e.size())); HIP_TRY(dalloc(&b.rows, Pz * NR_K));
+    HIP_TRY(dalloc(&b.gnode, (size_t)G));
+    HIP_TRY(dalloc(&b.xl, (size_t)xl_cap)); HIP_TRY(dalloc(&b.xl_off, xl_off.size()));
+    HIP_TRY(dalloc(&b.trk_start, trk_start.size()));
+    HIP_TRY(dalloc(&B.ne_off, ne_off.size())); HIP_TRY(dalloc(&B.ne_pos, Ez));
+    HIP_TRY(dalloc(&B.nn_off, (size_t)G)); HIP_TRY(dalloc(&B.nn_list, std::max<uint32_t>(list_off[G], 1)));
+    if (reap) {
+        HIP_TRY(dalloc(&B.e_pair, Ez)); HIP_TRY(dalloc(&B.occ, 2 * Ez));
+        if (c->d_occ_local) HIP_TRY(dalloc(&B.occ_local, 2 * Ez));
+        HIP_TRY(dalloc(&B.rm_off, (size_t)G)); HIP_TRY(dalloc(&B.rm_list, std::max<uint32_t>(list_off[G], 1)));
+    }
+    HIP_TRY(dalloc(&B.elems[0], (size_t)M)); HIP_TRY(dalloc(&B.elems[1], (size_t)M));
+    HIP_TRY(dalloc(&B.hist, std::max(sort_hist_words(std::max<int64_t>(M, 1)), sort_hist_words(1) * 4)));
+    HIP_TRY(dalloc(&B.tot, 256));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(B.blob, stage.data(), bytes, hipMemcpyHostToDevice, st));
+    auto view = [&](int k) { return reinterpret_cast<uint32_t*>(B.blob + parts[k].at); };
+    auto keep = [&](uint32_t* dst, int k, size_t words) -> hipError_t {   // a table the snapshot keeps: its own buffer
+        return words ? hipMemcpyAsync(dst, view(k), words * 4, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    };
+    HIP_TRY(keep(B.ne_off, P_NE, ne_off.size())); HIP_TRY(keep(b.xl_off, P_XLO, xl_off.size()));
+    HIP_TRY(keep(b.trk_start, P_TRK, trk_start.size())); HIP_TRY(keep(b.piece_off, P_POFF, piece_off.size()));
+    HIP_TRY(keep(b.piece_pair, P_PPAIR, piece_pair.size())); HIP_TRY(keep(b.pp_off, P_PP, pp_off.size()));
+    HIP_TRY(keep(b.span_off, P_SOFF, span_off.size())); HIP_TRY(keep(b.span_e, P_SE, span_e.size()));
+    HIP_TRY(keep(B.nn_off, P_LIST, (size_t)G));
+    if (reap) HIP_TRY(keep(B.rm_off, P_LIST, (size_t)G));
+#if ESC_MEASURE
+    HIP_TRY(hipStreamSynchronize(st));                       // (the probe's split: the upload's end)
+    g_rebuild_ms[1] = (rebuild_clock() - t0) * 1e3;
+    t0 = rebuild_clock();
+#endif
+    // ---- list, sort, place
+    RebuildDev R{};
+    R.flags = c->nodes.flags; R.label0 = c->nodes.label0; R.xl_off = c->nodes.xl_off; R.xl = c->nodes.xl;
+    R.cpu = c->nodes.cpu; R.mem = c->nodes.mem;
+    R.n_cap = NC; R.xl_len = c->xl_used;
+    R.ne_off = view(P_NE); R.xl_off_new = view(P_XLO); R.trk_start = view(P_TRK); R.start = view(P_START);
+    R.pair_lo = view(P_LO); R.piece_off = view(P_POFF); R.piece_pair = view(P_PPAIR);
+    R.n_pieces = n_pieces; R.n_elems = M; R.n_entries = E; R.xl_new_cap = xl_cap;
+    R.n_gp = n_gp; R.spare_total = (uint32_t)spare_total;
+    R.xl_new = b.xl; R.e_flags = b.e_flags; R.e_node = b.e_node; R.e_pair = B.e_pair; R.e_cpu = b.e_cpu;
+    R.e_mem = b.e_mem; R.e_pk = b.e_pk; R.ne_pos = B.ne_pos;
+    R.err = reinterpret_cast<uint32_t*>(B.blob + err_at);
+    HIP_TRY(launch_nodes_rebuild(R, B.elems, B.hist, B.tot, bit_width(max_pair), st));
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, R.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                       // the build's wait
+    if (err) {
+        std::snprintf(g_last_error, sizeof g_last_error, "nodes rebuild: the node table does not fit the mirrors' layout (%u)", err);
+        return ESC_E_HIP;
+    }
+    g_rebuild_ms[2] = (rebuild_clock() - t0) * 1e3;
+    t0 = rebuild_clock();
+    // ---- host mirrors: entry -> node in one copy, the map, allNodes[0] of every group
+    std::vector<uint32_t> h_e_node((size_t)E), ne_pos((size_t)M);
+    if (E) HIP_TRY(hipMemcpy(h_e_node.data(), b.e_node, (size_t)E * 4, hipMemcpyDeviceToHost));
+    if (M) HIP_TRY(hipMemcpy(ne_pos.data(), B.ne_pos, (size_t)M * 4, hipMemcpyDeviceToHost));
+    std::vector<GroupNode> gn((size_t)G);
+    for (int32_t g = 0; g < G; ++g) {
+        const uint32_t q = c->gi.gpair[g];
+        GroupNode& x = gn[g];
+        x.plo = std::max<int64_t>(pp_off[q], pc_lo);
+        x.phi = std::min<int64_t>(pp_off[q + 1], pc_hi);
+        if (x.phi < x.plo) x.phi = x.plo;
+        const bool any = pair_next[q] > pair_lo[q];
+        x.first = any ? (int64_t)h_e_node[pair_lo[q]] : INT64_MAX;      // sorted by node: the lowest
+        if (any && (x.first < 0 || x.first >= N)) return fail_hip(hipErrorUnknown, "nodes rebuild: entry mirror");
+        x.first_cpu = any ? c->h_ncpu[x.first] : 0;
+        x.first_mem = any ? c->h_nmem[x.first] : 0;
+    }
+    if (G) HIP_TRY(hipMemcpy(b.gnode, gn.data(), gn.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
+    g_rebuild_ms[3] = (rebuild_clock() - t0) * 1e3;
+    // ---- the swap: nothing below fails before the snapshot is whole again
+    drop_graphs(c);                                          // captured steps hold the old buffers
+    NodeBuf& o = c->nodes;
+    std::swap(o.e_flags, b.e_flags); std::swap(o.e_node, b.e_node); std::swap(o.e_cpu, b.e_cpu);
+    std::swap(o.e_mem, b.e_mem); std::swap(o.e_pk, b.e_pk); std::swap(o.piece_off, b.piece_off);
+    std::swap(o.piece_pair, b.piece_pair); std::swap(o.pp_off, b.pp_off); std::swap(o.span_off, b.span_off);
+    std::swap(o.span_e, b.span_e); std::swap(o.rows, b.rows); std::swap(o.gnode, b.gnode);
+    std::swap(o.xl, b.xl); std::swap(o.xl_off, b.xl_off); std::swap(o.trk_start, b.trk_start);
+    std::swap(c->d_ne_off, B.ne_off); std::swap(c->d_ne_pos, B.ne_pos);
+    std::swap(c->d_nn_off, B.nn_off); std::swap(c->d_nn_list, B.nn_list);
+    if (reap) {
+        std::swap(c->d_e_pair, B.e_pair); std::swap(c->d_occ, B.occ); std::swap(c->d_occ_local, B.occ_local);
+        std::swap(c->d_rm_off, B.rm_off); std::swap(c->d_rm_list, B.rm_list);
+        c->h_rm_off = list_off;
+    }
+    c->h_nn_off.swap(list_off);
+    c->h_nn_new.clear();
+    c->pair_lo.swap(pair_lo); c->pair_next.swap(pair_next); c->pair_end.swap(pair_end);
+    c->h_e_node.swap(h_e_node);
+    ne_off.resize((size_t)N + 1);                            // the host map covers the nodes so far (adds append)
+    c->ne_off.swap(ne_off);
+    c->ne_pos.swap(ne_pos);
+    c->ne_dev_nodes = N;                                     // the device copy is the one just built
+    c->ne_dev_pos = M;
+    std::copy(nflags.begin(), nflags.end(), c->h_nflags.begin());
+    std::copy(xl_off.begin(), xl_off.begin() + NC, c->h_xl_off.begin());
+    c->h_xl.swap(h_xl);
+    c->xl_used = c->n_xl = (int64_t)xw;
+    c->xl_cap = xl_cap;
+    c->h_gnode.swap(gn);
+    c->h_gn.clear();
+    c->n_entries = E;
+    c->n_pieces = n_pieces;
+    c->n_spans = (int64_t)span_off.size() - 1;
+    c->pc_lo = pc_lo;
+    c->pc_hi = pc_hi;
+    c->node_bytes = node_bytes;
+    c->e_pk_ok = pk_ok;
+    c->sel_valid = c->rm_valid = c->nn_valid = false;
+    c->sorted = false;
+    // ---- what is recounted over the new entries: a failure from here on leaves the node
+    // side stale (the occupancy words) or the orderings refused (the age index), as after a load
+    t0 = rebuild_clock();
+    if (reap && c->placed)
+        if (int32_t rc = occ_recount(c)) { c->stale |= STALE_NODES; return rc; }
+    g_rebuild_ms[4] = (rebuild_clock() - t0) * 1e3;
+    t0 = rebuild_clock();
+    release_sort(c);                                         // a fresh index: regions sized from the live counts
+    const int32_t rc = build_age_index(c);
+    g_rebuild_ms[5] = (rebuild_clock() - t0) * 1e3;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t esc_nodes_rebuild(esc_ctx* c) {
+    if (c && c->multi) return esc::multi_nodes_rebuild(c);
+    if (!c) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
+    return nodes_rebuild_one(c);
+}
+
+int32_t esc_nodes_room(const esc_ctx* c, int64_t* free_slots, int64_t* free_xl_words) {
+    if (c && c->multi) return esc_nodes_room(esc::multi_sub(c, 0), free_slots, free_xl_words);
+    if (!c) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nodes_loaded) return ESC_E_STATE;
+    if (free_slots) *free_slots = c->n_cap - c->n_nodes;
+    if (free_xl_words) *free_xl_words = c->xl_cap - c->xl_used;
+    return ESC_OK;
+}
+
+#if ESC_MEASURE
+// The last esc_nodes_rebuild of this thread, split (ms): host layout, upload, list + sort +
+// place, mirror download, occupancy recount, age-index build (measurement library only; not
+// in the header; scripts/rebuild_probe.py).
+int32_t esc_debug_rebuild_times(double* ms, int32_t n) {
+    if (!ms || n < 0) return ESC_E_INVAL;
+    for (int32_t k = 0; k < n && k < 6; ++k) ms[k] = g_rebuild_ms[k];
+    return ESC_OK;
+}
+#endif
 
 }  // extern "C"
 

@@ -5,7 +5,9 @@
 maps the event calls of the C ABI need: every ``esc_pods_*`` / ``esc_nodes_*`` call takes
 snapshot indices, and this queue is what maps a pod key or a node name to one, hands out and
 recycles pod ids, batches a scan's events into at most one call per kind and falls back to
-one full reload when ``ESC_E_LIMIT`` says the spare room ran out.
+one full reload when ``ESC_E_LIMIT`` says the spare room ran out.  With ``rebuild=True`` a
+node call that answers ``ESC_E_LIMIT`` is first answered by ``nodes_rebuild`` (the node side
+re-derived on the device, no pod reloaded) and retried once.
 
 It holds the current objects (plain-dict records, escalator_amd/objects.py) — the truth a
 reload is built from — and, beside them, what the device last saw of each.  Ingest
@@ -65,8 +67,11 @@ def _status(n: dict):
 
 
 class EventQueue:
-    def __init__(self, spare: float = 0.5):
+    def __init__(self, spare: float = 0.5, rebuild: bool = False):
         self.spare = float(spare)
+        self.rebuild = bool(rebuild)               # answer a node-side ESC_E_LIMIT with nodes_rebuild first
+        self.rebuilds = 0
+        self.rebuild_causes: list[str] = []        # the call that answered ESC_E_LIMIT, or "audit:<check>"
         self.pods: dict[str, dict] = {}            # the object store: key -> pod, name -> node
         self.nodes: dict[str, dict] = {}           # (insertion order = arrival order)
         self._dev_pods: dict[str, dict] = {}       # the records the device holds, as last flushed
@@ -166,6 +171,25 @@ class EventQueue:
         self.applied[kind] += n
         return rc
 
+    def _node_call(self, ctx, kind: str, n: int, slots: int, fn, *args):
+        """A nodes_add / nodes_relabel call: with ``rebuild`` on, its first ESC_E_LIMIT is
+        answered by one node-side rebuild (when the table has the `slots` free slots the call
+        needs: a rebuild does not grow the table) and one retry; the second reloads."""
+        try:
+            return self._call(kind, n, fn, *args)
+        except _Reload:
+            if not self.rebuild or (slots and ctx.nodes_room()[0] < slots):
+                raise
+        self.node_rebuild(ctx, kind)
+        return self._call(kind, n, fn, *args)
+
+    def node_rebuild(self, ctx, cause: str):
+        """One ``nodes_rebuild``: `cause` goes into ``rebuild_causes``.  Indices, pods, the
+        placement, the trackers and the instantiation times stay as they are."""
+        ctx.nodes_rebuild()
+        self.rebuilds += 1
+        self.rebuild_causes.append(cause)
+
     def _target(self, pod: dict) -> int:
         return self._node_idx.get(pod.get("node_name") or "", NONE) if pod.get("node_name") else NONE
 
@@ -208,7 +232,7 @@ class EventQueue:
         new = [m for m in self.nodes if m in dirty_n and m not in dev_n]
         if new:
             _, packed = ctx.pack([], [self.nodes[m] for m in new])
-            ids = self._call("nodes_add", len(new), ctx.nodes_add, packed)
+            ids = self._node_call(ctx, "nodes_add", len(new), len(new), ctx.nodes_add, packed)
             for m, j in zip(new, ids):
                 idx[m] = int(j)
                 self._idx_node[int(j)] = m
@@ -228,8 +252,8 @@ class EventQueue:
                 facts.append(m)
         if relabel:
             _, packed = ctx.pack([], [self.nodes[m] for m in relabel])
-            self._call("nodes_relabel", len(relabel), ctx.nodes_relabel, np.array([idx[m] for m in relabel], np.int64),
-                       packed)
+            self._node_call(ctx, "nodes_relabel", len(relabel), 0, ctx.nodes_relabel,
+                            np.array([idx[m] for m in relabel], np.int64), packed)
         if update:
             _, packed = ctx.pack([], [self.nodes[m] for m in update])
             self._call("nodes_update", len(update), ctx.nodes_update, np.array([idx[m] for m in update], np.int64),

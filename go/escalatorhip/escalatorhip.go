@@ -316,6 +316,9 @@ type Context struct {
 	cspecs unsafe.Pointer // C copy of the group specs, alive as long as the context
 	names  arena
 	sel    bool // SetSelections on: RunOnce returns the walks' first nodes
+	// NodeRebuild: NodesAdd / NodesRelabel answer their first ESC_E_LIMIT with NodesRebuild
+	// and one retry before they return ErrReload (off: ErrReload at once, as before)
+	NodeRebuild bool
 	selBuf []C.int64_t // RunOnce's selection buffer (grows once to the decisions' size)
 }
 
@@ -712,6 +715,14 @@ func (x *Context) NodesAdd(nodes []*v1.Node) ([]int64, error) {
 	}
 	err := x.pack(nil, nodes, nil, false, func(_ *C.esc_pod_soa, ns *C.esc_node_soa) error {
 		rc := C.esc_nodes_add(x.c, ns, (*C.int64_t)(unsafe.Pointer(ptr(ids))))
+		if rc == C.ESC_E_LIMIT && x.NodeRebuild { // the node side's spare room: rebuild it, retry once
+			if free, _, err := x.NodesRoom(); err == nil && free >= int64(len(nodes)) {
+				if err := x.NodesRebuild(); err != nil {
+					return err
+				}
+				rc = C.esc_nodes_add(x.c, ns, (*C.int64_t)(unsafe.Pointer(ptr(ids))))
+			}
+		}
 		if rc == C.ESC_E_LIMIT {
 			return ErrReload
 		}
@@ -733,11 +744,32 @@ func (x *Context) NodesRelabel(ids []int64, nodes []*v1.Node) error {
 	}
 	return x.pack(nil, nodes, nil, false, func(_ *C.esc_pod_soa, ns *C.esc_node_soa) error {
 		rc := C.esc_nodes_relabel(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), ns)
+		if rc == C.ESC_E_LIMIT && x.NodeRebuild { // as NodesAdd: rebuild the node side, retry once
+			if err := x.NodesRebuild(); err != nil {
+				return err
+			}
+			rc = C.esc_nodes_relabel(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), ns)
+		}
 		if rc == C.ESC_E_LIMIT {
 			return ErrReload
 		}
 		return rcErr("esc_nodes_relabel", rc)
 	})
+}
+
+// NodesRebuild re-derives the node side of the resident snapshot on the device
+// (esc_nodes_rebuild: the node half of the informer re-list, node_listers.go:33) with fresh
+// spare room; node indices, pods, the placement and the trackers stay.
+func (x *Context) NodesRebuild() error {
+	return rcErr("esc_nodes_rebuild", C.esc_nodes_rebuild(x.c))
+}
+
+// NodesRoom returns the free node-table slots and extra-label words (esc_nodes_room): a
+// rebuild does not grow the table, so more adds than free slots still need a Load.
+func (x *Context) NodesRoom() (freeSlots, freeXLWords int64, err error) {
+	var a, b C.int64_t
+	err = rcErr("esc_nodes_room", C.esc_nodes_room(x.c, &a, &b))
+	return int64(a), int64(b), err
 }
 
 // NodesDelete applies node Delete events by snapshot index.

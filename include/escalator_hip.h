@@ -534,6 +534,31 @@ int32_t esc_nodes_delete(esc_ctx* ctx, const int64_t* ids, int64_t n);
  * absent id; a device failure after the first change marks the node side stale (decisions
  * and reaping return ESC_E_STATE until esc_load_nodes). */
 int32_t esc_nodes_relabel(esc_ctx* ctx, const int64_t* ids, const esc_node_soa* nodes);
+/* The node half of the informer re-list (the reference's lister walks the informer's whole
+ * store on every List: pkg/k8s/node_listers.go:33, fed by pkg/k8s/cache.go:27,48): when
+ * esc_nodes_add / esc_nodes_relabel answer ESC_E_LIMIT because a label pair's spare entries
+ * (or the extra-label words, or a K5 region) ran out, esc_nodes_rebuild re-derives the node
+ * side from the RESIDENT node table on the device, in place, with fresh spare room sized
+ * from the live counts and the esc_set_spare fraction — no pod is read or written.
+ * Kept: node indices (absent slots stay absent, deleted slots are not reused), the table's
+ * capacity, pod blocks and replicas, the K1 plan / calibration / touch tables, the
+ * placement's PodRefs and runs, taint times, no-delete bytes, instantiation times, the
+ * tracker list, esc_set_state, group ownership (esc_group_owner, the exchange layout).
+ * Rebuilt: the pair-major entries sorted by (pair, node) with ceil(live * f) + 4 spare entries
+ * per group pair, pieces and spans, the node -> entries map, every group's allNodes[0], the
+ * new-node and removal list offsets, the tracker index and bit, the extra-label words
+ * (compacted), the occupancy words (recounted over the kept PodRefs) and the age index.
+ * Captured graphs are dropped; selections, removal and new-node results and the last
+ * ordering are invalidated.  All or nothing up to the swap of the new buffers: a device
+ * error before it (ESC_E_HIP, ESC_E_NOMEM) leaves the snapshot as it was; a failed age-index
+ * build after it leaves orderings refused as after a load.  The device node table supplies
+ * the values, the host mirrors the counts that fix the layout: a mirror that disagrees with
+ * the table is reported (ESC_E_HIP), not repaired.  ESC_E_NODEV without a device,
+ * ESC_E_STATE without a node table or on a stale context.  A rebuild does not grow the
+ * table: esc_nodes_room tells the free table slots and extra-label words (either may be
+ * null); an add that needs more slots than are free still needs esc_load_nodes. */
+int32_t esc_nodes_rebuild(esc_ctx* ctx);
+int32_t esc_nodes_room(const esc_ctx* ctx, int64_t* free_slots, int64_t* free_xl_words);
 
 /* ------------------------------------------- dry-mode taintTracker (§8f rank 4)
  * nodeGroup.taintTracker (controller.go:35) as interned (node, group) pairs on the
