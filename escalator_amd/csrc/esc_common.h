@@ -218,4 +218,25 @@ ESC_HD bool pf_default_ok(uint32_t f) {
 }
 ESC_HD uint32_t nf_xlbl(uint32_t f) { return (f >> ESC_NF_XLBL_SHIFT) & ESC_PF_CNT_MASK; }
 
+// ------------------------------------------------- node-side layout constants
+// What K2 and the host's layout plan (esc_node_layout.h) share: a piece is a run of entries
+// of one pair, a span the whole pieces one K2 wave reduces.
+constexpr int NODE_PIECE = 1024;           // entries per piece at most (K2's counts: 21 bits each)
+constexpr int PIECE_ALIGN = 256;           // no piece crosses a multiple of it (plan_node_layout)
+static_assert(NODE_PIECE % PIECE_ALIGN == 0, "the alignment bounds every piece");
+#ifndef ESC_NODE_SPAN
+#define ESC_NODE_SPAN 256                  // (timing builds may override; the runtime builds the spans too)
+#endif
+constexpr int NODE_SPAN = ESC_NODE_SPAN;   // entries per K2 wave (whole pieces, <= 63 of them)
+
+// Per-group node facts that are fixed for a loaded snapshot (esc_node_layout.h, group_node):
+// this rank's piece range of the group's pair (empty when another rank owns the pair) and
+// allNodes[0] (controller.go:207-211, from the whole table on every rank) with its
+// allocatable, so K3 needs no dependent index chase.
+struct GroupNode {
+    int64_t first;             // lowest member node index (INT64_MAX: no member)
+    int64_t first_cpu, first_mem;
+    int64_t plo, phi;          // this rank's pieces of the group's pair
+};
+
 }  // namespace esc

@@ -307,18 +307,10 @@ struct PodDev {
 //    K2's spans of whole pieces come out full); this rank reduces the pieces
 //    [pc_lo, pc_hi) of the pairs [q_lo, q_hi) it owns.  K3 joins each group to its pair's
 //    pieces.
-// Per-group node facts that are fixed for a loaded snapshot (esc_load_nodes): this rank's
-// piece range of the group's pair (empty when another rank owns the pair) and allNodes[0]
-// (controller.go:207-211, from the whole table on every rank) with its allocatable, so K3
-// needs no dependent index chase.
-struct GroupNode {
-    int64_t first;             // lowest member node index (INT64_MAX: no member)
-    int64_t first_cpu, first_mem;
-    int64_t plo, phi;          // this rank's pieces of the group's pair
-};
-
+// (PIECE_ALIGN, NODE_PIECE, NODE_SPAN and GroupNode: esc_common.h, shared with the host's
+// layout plan, esc_node_layout.h.)
 struct NodeDev {
-    const GroupNode* gnode;    // [G]
+    const GroupNode* gnode;    // [G] per-group facts fixed by the snapshot
     const uint32_t* flags;
     const uint32_t* label0;
     const int64_t*  cpu;
@@ -362,13 +354,6 @@ enum NodeRow : int {
     NR_COUNTS,                                             // unt | taint << 21 | cord << 42
     NR_K
 };
-constexpr int NODE_PIECE = 1024;
-constexpr int PIECE_ALIGN = 256;           // no piece crosses a multiple of it (esc_load_nodes)
-static_assert(NODE_PIECE % PIECE_ALIGN == 0, "the alignment bounds every piece");
-#ifndef ESC_NODE_SPAN
-#define ESC_NODE_SPAN 256                  // (timing builds may override; the runtime builds the spans too)
-#endif
-constexpr int NODE_SPAN = ESC_NODE_SPAN;   // entries per K2 wave (whole pieces, <= 63 of them)
 constexpr int NR_CNT_BITS = 21;
 constexpr uint64_t NR_CNT_MASK = (uint64_t(1) << NR_CNT_BITS) - 1;
 

@@ -25,6 +25,7 @@
 #include "esc_internal.h"
 #include "esc_kernels.h"
 #include "esc_multi.h"
+#include "esc_node_layout.h"
 
 #ifndef ESC_MEASURE
 #define ESC_MEASURE 0   // 1: the measurement library (Makefile ABLATIONS=1) reads its knobs
@@ -55,6 +56,13 @@ hipError_t dalloc(T** p, size_t n) {
     return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T));
 }
 
+// A device copy of a host vector.
+template <class T>
+hipError_t dcopy(T** p, const std::vector<T>& v) {
+    const hipError_t e = dalloc(p, v.size());
+    return e != hipSuccess || v.empty() ? e : hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
 template <class T>
 void dfree(T*& p) {
     if (p) hipFree(p);
@@ -73,24 +81,36 @@ struct PodBuf {
     }
 };
 
-struct NodeBuf {
-    // node table (snapshot order)
-    uint32_t *flags = nullptr, *label0 = nullptr, *xl = nullptr, *xl_off = nullptr, *trk_start = nullptr;
-    int64_t *cpu = nullptr, *mem = nullptr, *created = nullptr;
-    int32_t *trk_node = nullptr, *trk_group = nullptr;
-    // pair-major entries, pieces, tracker by group, K2 rows
+// What is derived from the node table and the layout (esc_node_layout.h): the buffers a
+// rebuild builds anew and swaps in as one (esc_nodes_rebuild).
+struct NodeDerived {
+    // pair-major entries, pieces, K2 rows
     uint32_t *e_flags = nullptr, *e_node = nullptr, *piece_off = nullptr, *piece_pair = nullptr, *pp_off = nullptr;
     uint32_t* span_off = nullptr;                // K2 waves' piece ranges
     uint32_t* span_e = nullptr;                  // and their entry ranges
     int64_t *e_cpu = nullptr, *e_mem = nullptr, *rows = nullptr;
     uint4* e_pk = nullptr;                       // the entries packed 16 B each (NodeDev::e_pk)
     GroupNode* gnode = nullptr;
+    // the extra labels (compacted by a rebuild), their offsets and the tracker's per-node index
+    uint32_t *xl = nullptr, *xl_off = nullptr, *trk_start = nullptr;
     void release() {
         dfree(gnode);
-        dfree(flags); dfree(label0); dfree(xl); dfree(xl_off); dfree(trk_start); dfree(cpu); dfree(mem);
-        dfree(created); dfree(trk_node); dfree(trk_group);
         dfree(e_flags); dfree(e_node); dfree(piece_off); dfree(piece_pair); dfree(pp_off); dfree(span_off); dfree(span_e);
         dfree(e_cpu); dfree(e_mem); dfree(rows); dfree(e_pk);
+        dfree(xl); dfree(xl_off); dfree(trk_start);
+    }
+};
+
+struct NodeBuf {
+    // node table (snapshot order), tracker by (node, group)
+    uint32_t *flags = nullptr, *label0 = nullptr;
+    int64_t *cpu = nullptr, *mem = nullptr, *created = nullptr;
+    int32_t *trk_node = nullptr, *trk_group = nullptr;
+    NodeDerived d;
+    void release() {
+        dfree(flags); dfree(label0); dfree(cpu); dfree(mem);
+        dfree(created); dfree(trk_node); dfree(trk_group);
+        d.release();
     }
 };
 
@@ -311,7 +331,6 @@ struct esc_ctx {
     std::vector<uint32_t> h_e_node;                           // pair-major entry -> node (NONE: spare)
     std::vector<uint32_t> pair_next, pair_end;                // group pair -> next spare entry, range end
     std::vector<uint32_t> pair_lo;                            // group pair -> its first entry
-    uint32_t nodes_piece_lo(uint32_t q) const { return pair_lo[q]; }
     std::vector<uint32_t> h_gn;                               // group regions' nodes (lazy mirror of d_g_memb)
     // per-function drop-ins: the list reducer (esc_list.hip); esc_order_by_creation runs
     // on a one-group list context
@@ -503,17 +522,17 @@ PodDev pod_dev(const esc_ctx* c, int replica) {
 
 NodeDev node_dev(const esc_ctx* c) {
     NodeDev n;
-    n.gnode = c->nodes.gnode;
+    n.gnode = c->nodes.d.gnode;
     n.flags = c->nodes.flags; n.label0 = c->nodes.label0; n.cpu = c->nodes.cpu; n.mem = c->nodes.mem;
-    n.created = c->nodes.created; n.xl = c->nodes.xl; n.xl_off = c->nodes.xl_off;
-    n.trk_node = c->nodes.trk_node; n.trk_group = c->nodes.trk_group; n.trk_start = c->nodes.trk_start;
+    n.created = c->nodes.created; n.xl = c->nodes.d.xl; n.xl_off = c->nodes.d.xl_off;
+    n.trk_node = c->nodes.trk_node; n.trk_group = c->nodes.trk_group; n.trk_start = c->nodes.d.trk_start;
     n.n_trk = c->n_trk;
     n.lo = c->node_lo; n.hi = c->node_hi;
-    n.e_flags = c->nodes.e_flags; n.e_cpu = c->nodes.e_cpu; n.e_mem = c->nodes.e_mem; n.e_node = c->nodes.e_node;
-    n.e_pk = c->e_pk_ok ? c->nodes.e_pk : nullptr;
-    n.piece_off = c->nodes.piece_off; n.piece_pair = c->nodes.piece_pair; n.pp_off = c->nodes.pp_off;
+    n.e_flags = c->nodes.d.e_flags; n.e_cpu = c->nodes.d.e_cpu; n.e_mem = c->nodes.d.e_mem; n.e_node = c->nodes.d.e_node;
+    n.e_pk = c->e_pk_ok ? c->nodes.d.e_pk : nullptr;
+    n.piece_off = c->nodes.d.piece_off; n.piece_pair = c->nodes.d.piece_pair; n.pp_off = c->nodes.d.pp_off;
     n.n_pieces = c->n_pieces; n.pc_lo = c->pc_lo; n.pc_hi = c->pc_hi;
-    n.span_off = c->nodes.span_off; n.span_e = c->nodes.span_e; n.n_spans = c->n_spans;
+    n.span_off = c->nodes.d.span_off; n.span_e = c->nodes.d.span_e; n.n_spans = c->n_spans;
     n.q_lo = c->q_lo; n.q_hi = c->q_hi;
     return n;
 }
@@ -1092,6 +1111,18 @@ std::vector<int64_t> pair_counts(const esc_ctx* c, const esc_node_soa* s) {
     return cnt;
 }
 
+// A planned layout (esc_node_layout.h) becomes the context's, once its device tables are in
+// place (esc_load_nodes, esc_nodes_rebuild).  Nothing here fails.
+void commit_layout(esc_ctx* c, NodeLayout& L, bool pk_ok) {
+    c->pair_lo.swap(L.pair_lo); c->pair_next.swap(L.pair_next); c->pair_end.swap(L.pair_end);
+    c->n_entries = L.n_entries; c->n_pieces = L.n_pieces; c->n_spans = (int64_t)L.span_off.size() - 1;
+    c->pc_lo = L.pc_lo; c->pc_hi = L.pc_hi;
+    c->node_bytes = L.node_bytes;
+    c->e_pk_ok = pk_ok;
+    c->h_nn_off.swap(L.list_off);
+    c->h_gn.clear();
+}
+
 // Pod accumulator slots: one per group pair + one for the default filter.
 int64_t pod_slots(const esc_ctx* c) { return (int64_t)c->gi.n_gp + 1; }
 
@@ -1378,7 +1409,7 @@ int32_t enqueue_step(esc_ctx* c, int r, bool decide, bool copy_out) {
         ng_trace = c->d_ttrace + 3 * nt;
     }
 #endif
-    HIP_TRY(launch_step_tail(g, n, f, true, c->d_wide_pod, c->d_pwords, c->nodes.rows, c->d_trk_acc, c->d_pchunks,
+    HIP_TRY(launch_step_tail(g, n, f, true, c->d_wide_pod, c->d_pwords, c->nodes.d.rows, c->d_trk_acc, c->d_pchunks,
                              ord ? c->n_psmall : 0, c->d_grp_off, c->d_g_memb, c->d_ord, c->d_seg, st));
     if (int32_t rc = mark()) return rc;
     if (ord) {                                       // split groups, mid-size packed chunks
@@ -1395,7 +1426,7 @@ int32_t enqueue_step(esc_ctx* c, int r, bool decide, bool copy_out) {
     // the node groups do not depend on the exchange, so they run with K4 after it in ONE
     // launch (esc_decide) — one kernel boundary less on the rank's critical path.
     if (decide) {
-        HIP_TRY(launch_node_groups(g, n, own_list(c), c->nodes.rows, c->d_trk_acc, c->d_nwords,
+        HIP_TRY(launch_node_groups(g, n, own_list(c), c->nodes.d.rows, c->d_trk_acc, c->d_nwords,
                                    NGDecide{c->d_pwords, c->d_dec, cdec, sel_out(c), ng_trace}, st));
         if (int32_t rc = mark()) return rc;
     }
@@ -1977,78 +2008,31 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
             return ESC_E_INVAL;                      // must be sorted by (node, group), unique
     }
     // Pair-major entries: one per (label pair, node) of the whole table, sorted by
-    // (pair, node) — the group-independent index K2 streams.  Pieces are
-    // runs of entries of one pair that never cross a multiple of PIECE_ALIGN (256) entries,
-    // so K2's spans (whole pieces, <= NODE_SPAN entries) come out full: cut only
-    // at pairs, spans averaged 72 % of NODE_SPAN at config 4 (a pair's run seldom fits
-    // beside the previous one), 1 460 tail blocks of mostly-masked loads instead of ~1 060
-    // (round 6); a pair cut in two is summed from both rows by k_node_groups, as any
-    // multi-piece pair.  This rank reduces the pieces that start in its 1/world share of
-    // the entries.
+    // (pair, node) — the group-independent index K2 streams.  A group pair's
+    // live entries are followed by its spare ones (esc_set_spare: flagged ESC_NF_ABSENT, taken
+    // in order by added nodes, whose indices are above every loaded one, so a pair's entries
+    // stay in snapshot order); the layout itself is plan_node_layout's (esc_node_layout.h).
     std::vector<uint64_t> ent;
     ent.reserve((size_t)n + (size_t)s->n_xl);
-    const uint32_t n_gp0 = c->gi.n_gp;
-    std::vector<int64_t> pair_cnt(n_gp0, 0);
     for (int64_t i = 0; i < n; ++i) {
         if (s->flags[i] & ESC_NF_ABSENT) return ESC_E_INVAL;   // the context owns that bit
         if (s->label0[i] == NONE) continue;
         ent.push_back(((uint64_t)s->label0[i] << 32) | (uint64_t)i);
-        if (s->label0[i] < n_gp0) ++pair_cnt[s->label0[i]];
         const uint32_t nx = nf_xlbl(s->flags[i]);
-        for (uint32_t k = 0; k < nx; ++k) {
-            const uint32_t q = s->xl_pair[xl_off[i] + k];
-            ent.push_back(((uint64_t)q << 32) | (uint64_t)i);
-            if (q < n_gp0) ++pair_cnt[q];
-        }
-    }
-    // spare entries (esc_set_spare): after each group pair's entries, flagged ESC_NF_ABSENT,
-    // taken in order by added nodes (whose indices are above every loaded one, so a
-    // pair's entries stay in snapshot order)
-    const double sf = c->spare_frac;
-    for (uint32_t q = 0; q < n_gp0 && sf > 0; ++q) {
-        const int64_t sp = (int64_t)std::ceil((double)pair_cnt[q] * sf) + 4;
-        for (int64_t k = 0; k < sp; ++k) ent.push_back(((uint64_t)q << 32) | 0xFFFFFFFFull);
+        for (uint32_t k = 0; k < nx; ++k) ent.push_back(((uint64_t)s->xl_pair[xl_off[i] + k] << 32) | (uint64_t)i);
     }
     std::sort(ent.begin(), ent.end());
-    const int64_t E = (int64_t)ent.size();
-    if (E >= (int64_t)0xFFFFFFFF) return ESC_E_LIMIT;
-    std::vector<uint32_t> e_flags(std::max<int64_t>(E, 1)), e_node(std::max<int64_t>(E, 1));
-    std::vector<int64_t> e_cpu(std::max<int64_t>(E, 1)), e_mem(std::max<int64_t>(E, 1));
-    std::vector<uint32_t> piece_off, piece_pair;
-    for (int64_t k = 0; k < E; ++k) {
-        const uint32_t q = (uint32_t)(ent[k] >> 32), i = (uint32_t)ent[k];
-        if (k == 0 || q != piece_pair.back() || k % PIECE_ALIGN == 0) {
-            piece_off.push_back((uint32_t)k);
-            piece_pair.push_back(q);
-        }
-        if (i == NONE) {                             // spare entry
-            e_flags[k] = ESC_NF_ABSENT;
-            e_node[k] = NONE;
-            e_cpu[k] = e_mem[k] = 0;
-            continue;
-        }
-        e_flags[k] = s->flags[i];
-        e_node[k] = i;
-        e_cpu[k] = s->cpu[i];
-        e_mem[k] = s->mem[i];
-    }
-    const int64_t n_pieces = (int64_t)piece_pair.size();
-    piece_off.push_back((uint32_t)E);
-    // node -> its entry positions (esc_nodes_update patches the entries' copies)
-    std::vector<uint32_t> ne_off((size_t)n + 1, 0), ne_pos((size_t)std::max<int64_t>(E, 1));
-    for (int64_t k = 0; k < E; ++k)
-        if ((uint32_t)ent[k] != NONE) ++ne_off[(uint32_t)ent[k] + 1];
-    for (int64_t i = 0; i < n; ++i) ne_off[i + 1] += ne_off[i];
-    {
-        std::vector<uint32_t> fill(ne_off.begin(), ne_off.end() - 1);
-        for (int64_t k = 0; k < E; ++k)
-            if ((uint32_t)ent[k] != NONE) ne_pos[fill[(uint32_t)ent[k]]++] = (uint32_t)k;
-    }
-    ne_pos.resize(ne_off[n]);
+    const int64_t M = (int64_t)ent.size();
     const uint32_t n_gp = c->gi.n_gp;
-    std::vector<uint32_t> pp_off((size_t)n_gp + 1);
-    for (uint32_t q = 0; q <= n_gp; ++q)
-        pp_off[q] = (uint32_t)(std::lower_bound(piece_pair.begin(), piece_pair.end(), q) - piece_pair.begin());
+    const std::vector<int64_t> pair_cnt = pair_counts(c, s);
+    int64_t n_grouped = 0;                           // the group pairs' live entries sort first
+    for (int64_t x : pair_cnt) n_grouped += x;
+    std::vector<TailRun> tail;                       // behind them: one run per other pair
+    for (int64_t k = n_grouped; k < M; ++k) {
+        const uint32_t q = (uint32_t)(ent[k] >> 32);
+        if (tail.empty() || tail.back().pair != q) tail.push_back(TailRun{q, 0});
+        ++tail.back().len;
+    }
     // This rank's share of the index: the pieces of the group pairs it owns, a
     // contiguous pair range balanced by entry count, the same split on every rank.  Its K2
     // streams only those, its node words are exact for those groups and zero for the others
@@ -2056,46 +2040,45 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
     // resident on every rank: allNodes[0] and the reaping read it.
     uint32_t q_lo = 0, q_hi = n_gp;
     owned_pairs(pair_cnt, c->world, c->rank, q_lo, q_hi);
-    const int64_t pc_lo = pp_off[q_lo], pc_hi = pp_off[q_hi];
     bool pk_ok = true;                               // K2's packed entries (NodeDev::e_pk)
     for (int64_t i = 0; i < n && pk_ok; ++i) pk_ok = entry_cpu_packs(s->cpu[i]);
-    // algorithmic bytes K2 streams per decision: per piece its pair and offset, per entry 16 B
-    // packed (flags, cpu, memory in one record) or 20 B (the three arrays)
-    const int64_t per_entry = pk_ok ? 16 : 20;
-    int64_t node_bytes = 0;
-    for (int64_t p = pc_lo; p < pc_hi; ++p) {
-        node_bytes += 8;                             // piece_pair + piece_off
-        if (piece_pair[p] < n_gp) node_bytes += per_entry * (int64_t)(piece_off[p + 1] - piece_off[p]);
-    }
-    // K2 spans: consecutive whole pieces of the group pairs (a prefix: pieces are pair-sorted
-    // and ids >= n_gp come last), <= NODE_SPAN entries (or one larger piece) and <= 63
-    // pieces per wave
-    std::vector<uint32_t> span_off(1, (uint32_t)pc_lo);
+    // the limits are checked here, from host data alone: a refused load leaves the previous
+    // snapshot intact
+    const double sf = c->spare_frac;
+    NodeLayout L;
+    if (const int32_t rc = plan_node_layout(L, pair_cnt, sf, tail, q_lo, q_hi, pk_ok, c->gi.gpair.data(), (int32_t)G))
+        return rc;
+    // capacity for added nodes (esc_nodes_add): table slots and extra-label words
+    const int64_t n_cap = table_slots(n, sf), xl_cap = label_words(s->n_xl, sf);
+    if (n_cap >= (int64_t)0x7FFFFFFF) return ESC_E_LIMIT;
+    const int64_t E = L.n_entries;
+    // the entries' copies of their nodes (spare entries: absent, no node) and node -> its
+    // entry positions (esc_nodes_update patches the entries' copies)
+    const size_t Ez = (size_t)std::max<int64_t>(E, 1);
+    std::vector<uint32_t> e_flags(Ez, ESC_NF_ABSENT), e_node(Ez, NONE);
+    std::vector<int64_t> e_cpu(Ez, 0), e_mem(Ez, 0);
+    std::vector<uint32_t> ne_off((size_t)n + 1, 0), ne_pos((size_t)std::max<int64_t>(M, 1));
+    for (int64_t k = 0; k < M; ++k) ++ne_off[(uint32_t)ent[k] + 1];
+    for (int64_t i = 0; i < n; ++i) ne_off[i + 1] += ne_off[i];
     {
-        int64_t p_end = pc_lo, acc = 0;
-        while (p_end < pc_hi && piece_pair[p_end] < n_gp) ++p_end;
-        int64_t np = 0;
-        for (int64_t p = pc_lo; p < p_end; ++p) {
-            const int64_t len = (int64_t)piece_off[p + 1] - piece_off[p];
-            if (acc > 0 && (acc + len > NODE_SPAN || np == 63)) { span_off.push_back((uint32_t)p); acc = 0; np = 0; }
-            acc += len;
-            ++np;
+        std::vector<uint32_t> fill(ne_off.begin(), ne_off.end() - 1);
+        uint32_t at = 0, prev = NONE;
+        for (int64_t k = 0; k < M; ++k) {
+            const uint32_t q = (uint32_t)(ent[k] >> 32), i = (uint32_t)ent[k];
+            if (k == n_grouped) at = (uint32_t)(E - (M - n_grouped));        // the tail
+            else if (k < n_grouped && q != prev) at = L.pair_lo[q];
+            prev = q;
+            e_flags[at] = s->flags[i];
+            e_node[at] = i;
+            e_cpu[at] = s->cpu[i];
+            e_mem[at] = s->mem[i];
+            ne_pos[fill[i]++] = at++;
         }
-        if (p_end > pc_lo) span_off.push_back((uint32_t)p_end);
     }
+    ne_pos.resize((size_t)M);
     // dry-mode tracker: each tracked node's first entry (the (node, group) list is node-sorted)
-    std::vector<uint32_t> trk_start(std::max<int64_t>(n + (sf > 0 ? (int64_t)std::ceil((double)n * sf) + 64 : 0), 1),
-                                    NONE);
+    std::vector<uint32_t> trk_start((size_t)std::max<int64_t>(n_cap, 1), NONE);
     for (int64_t k = s->n_trk - 1; k >= 0; --k) trk_start[s->trk_node[k]] = (uint32_t)k;
-    // the new-node pass's list offsets: a group's list holds at most its pair's entry capacity
-    // (checked here, from host data alone: a refused load leaves the previous snapshot intact)
-    std::vector<uint32_t> nn_off((size_t)G + 1, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-        const uint32_t q = c->gi.gpair[g];
-        const uint64_t end = (uint64_t)nn_off[g] + (piece_off[pp_off[q + 1]] - piece_off[pp_off[q]]);
-        if (end >= 0xFFFFFFFFull) return ESC_E_LIMIT;
-        nn_off[g + 1] = (uint32_t)end;
-    }
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     drop_graphs(c);
@@ -2104,20 +2087,17 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
     release_placement(c);
     release_new_nodes(c);
     c->nodes.release();
-    // capacity for added nodes (esc_nodes_add): table slots and extra-label words
-    const int64_t n_cap = n + (sf > 0 ? (int64_t)std::ceil((double)n * sf) + 64 : 0);
-    const int64_t xl_cap = s->n_xl + (sf > 0 ? (int64_t)std::ceil((double)s->n_xl * sf) + 256 : 0);
-    if (n_cap >= (int64_t)0x7FFFFFFF) return ESC_E_LIMIT;
     NodeBuf& b = c->nodes;
+    NodeDerived& d = b.d;
     HIP_TRY(dalloc(&b.flags, n_cap)); HIP_TRY(dalloc(&b.label0, n_cap)); HIP_TRY(dalloc(&b.cpu, n_cap));
-    HIP_TRY(dalloc(&b.mem, n_cap)); HIP_TRY(dalloc(&b.created, n_cap)); HIP_TRY(dalloc(&b.xl, xl_cap));
-    HIP_TRY(dalloc(&b.xl_off, n_cap)); HIP_TRY(dalloc(&b.trk_node, s->n_trk)); HIP_TRY(dalloc(&b.trk_group, s->n_trk));
+    HIP_TRY(dalloc(&b.mem, n_cap)); HIP_TRY(dalloc(&b.created, n_cap)); HIP_TRY(dalloc(&d.xl, xl_cap));
+    HIP_TRY(dalloc(&d.xl_off, n_cap)); HIP_TRY(dalloc(&b.trk_node, s->n_trk)); HIP_TRY(dalloc(&b.trk_group, s->n_trk));
     if (n_cap > n) {                                 // free slots: absent, no labels
         std::vector<uint32_t> fa(n_cap - n, ESC_NF_ABSENT), la(n_cap - n, NONE);
         HIP_TRY(hipMemcpy(b.flags + n, fa.data(), fa.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b.label0 + n, la.data(), la.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemset(b.cpu + n, 0, (n_cap - n) * 8)); HIP_TRY(hipMemset(b.mem + n, 0, (n_cap - n) * 8));
-        HIP_TRY(hipMemset(b.created + n, 0, (n_cap - n) * 8)); HIP_TRY(hipMemset(b.xl_off + n, 0, (n_cap - n) * 4));
+        HIP_TRY(hipMemset(b.created + n, 0, (n_cap - n) * 8)); HIP_TRY(hipMemset(d.xl_off + n, 0, (n_cap - n) * 4));
     }
     if (n) {
         HIP_TRY(hipMemcpy(b.flags, s->flags, n * 4, hipMemcpyHostToDevice));
@@ -2125,60 +2105,35 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
         HIP_TRY(hipMemcpy(b.cpu, s->cpu, n * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b.mem, s->mem, n * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b.created, s->created_ns, n * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b.xl_off, xl_off.data(), n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d.xl_off, xl_off.data(), n * 4, hipMemcpyHostToDevice));
     }
-    if (s->n_xl) HIP_TRY(hipMemcpy(b.xl, s->xl_pair, s->n_xl * 4, hipMemcpyHostToDevice));
+    if (s->n_xl) HIP_TRY(hipMemcpy(d.xl, s->xl_pair, s->n_xl * 4, hipMemcpyHostToDevice));
     if (s->n_trk) {
         HIP_TRY(hipMemcpy(b.trk_node, s->trk_node, s->n_trk * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b.trk_group, s->trk_group, s->n_trk * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(dalloc(&b.trk_start, trk_start.size()));
-    HIP_TRY(hipMemcpy(b.trk_start, trk_start.data(), trk_start.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(dalloc(&b.e_flags, e_flags.size())); HIP_TRY(dalloc(&b.e_node, e_node.size()));
-    HIP_TRY(dalloc(&b.e_cpu, e_cpu.size())); HIP_TRY(dalloc(&b.e_mem, e_mem.size()));
-    HIP_TRY(hipMemcpy(b.e_flags, e_flags.data(), e_flags.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b.e_node, e_node.data(), e_node.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b.e_cpu, e_cpu.data(), e_cpu.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b.e_mem, e_mem.data(), e_mem.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(dcopy(&d.trk_start, trk_start));
+    HIP_TRY(dcopy(&d.e_flags, e_flags)); HIP_TRY(dcopy(&d.e_node, e_node));
+    HIP_TRY(dcopy(&d.e_cpu, e_cpu)); HIP_TRY(dcopy(&d.e_mem, e_mem));
     {   // the packed copy K2 reads (kept current by entry_patch even when not in use)
         std::vector<uint4> pk(e_flags.size());
         for (size_t k = 0; k < pk.size(); ++k)
             pk[k] = make_uint4(e_flags[k], (uint32_t)e_cpu[k], (uint32_t)(uint64_t)e_mem[k],
                                (uint32_t)((uint64_t)e_mem[k] >> 32));
-        HIP_TRY(dalloc(&b.e_pk, pk.size()));
-        HIP_TRY(hipMemcpy(b.e_pk, pk.data(), pk.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        HIP_TRY(dcopy(&d.e_pk, pk));
     }
-    c->e_pk_ok = pk_ok;
-    HIP_TRY(dalloc(&b.piece_off, piece_off.size())); HIP_TRY(dalloc(&b.piece_pair, std::max<size_t>(piece_pair.size(), 1)));
-    HIP_TRY(dalloc(&b.pp_off, pp_off.size()));
-    HIP_TRY(hipMemcpy(b.piece_off, piece_off.data(), piece_off.size() * 4, hipMemcpyHostToDevice));
-    if (n_pieces) HIP_TRY(hipMemcpy(b.piece_pair, piece_pair.data(), piece_pair.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b.pp_off, pp_off.data(), pp_off.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(dalloc(&b.span_off, span_off.size()));
-    HIP_TRY(hipMemcpy(b.span_off, span_off.data(), span_off.size() * 4, hipMemcpyHostToDevice));
-    {
-        std::vector<uint32_t> span_e(span_off.size());
-        for (size_t w = 0; w < span_off.size(); ++w) span_e[w] = piece_off[span_off[w]];
-        HIP_TRY(dalloc(&b.span_e, span_e.size()));
-        HIP_TRY(hipMemcpy(b.span_e, span_e.data(), span_e.size() * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(dalloc(&b.rows, (size_t)std::max<int64_t>(n_pieces, 1) * NR_K));
-    {   // per-group facts fixed by this snapshot: this rank's pieces of the group's pair and
-        // allNodes[0] (controller.go:207-211) = the pair's first entry (lowest node index)
+    HIP_TRY(dcopy(&d.piece_off, L.piece_off)); HIP_TRY(dcopy(&d.piece_pair, L.piece_pair)); HIP_TRY(dcopy(&d.pp_off, L.pp_off));
+    HIP_TRY(dcopy(&d.span_off, L.span_off)); HIP_TRY(dcopy(&d.span_e, L.span_e));
+    HIP_TRY(dalloc(&d.rows, (size_t)std::max<int64_t>(L.n_pieces, 1) * NR_K));
+    {   // per-group facts fixed by this snapshot (group_node): allNodes[0] is the pair's first
+        // entry when that one is live, not spare
         std::vector<GroupNode> gn(G);
         for (uint32_t g = 0; g < G; ++g) {
-            const uint32_t q = c->gi.gpair[g], p0 = pp_off[q], p1 = pp_off[q + 1];
-            GroupNode& x = gn[g];
-            x.plo = std::max<int64_t>(p0, pc_lo);
-            x.phi = std::min<int64_t>(p1, pc_hi);
-            if (x.phi < x.plo) x.phi = x.plo;
-            const bool any = p1 > p0 && e_node[piece_off[p0]] != NONE;     // not only spare entries
-            x.first = any ? (int64_t)e_node[piece_off[p0]] : INT64_MAX;
-            x.first_cpu = any ? s->cpu[x.first] : 0;
-            x.first_mem = any ? s->mem[x.first] : 0;
+            const uint32_t q = c->gi.gpair[g];
+            const uint32_t first = L.pair_next[q] > L.pair_lo[q] ? e_node[L.pair_lo[q]] : NONE;
+            gn[g] = group_node(L, q, first, first != NONE ? s->cpu[first] : 0, first != NONE ? s->mem[first] : 0);
         }
-        HIP_TRY(dalloc(&b.gnode, gn.size()));
-        HIP_TRY(hipMemcpy(b.gnode, gn.data(), gn.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
+        HIP_TRY(dcopy(&d.gnode, gn));
         c->h_gnode.swap(gn);
     }
     {   // the instantiation-time fact (every slot unknown, the spare ones included) and the
@@ -2186,21 +2141,12 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
         std::vector<int64_t> unknown((size_t)std::max<int64_t>(n_cap, 1), INT64_MIN);
         HIP_TRY(dalloc(&c->d_inst, unknown.size()));
         HIP_TRY(hipMemcpy(c->d_inst, unknown.data(), unknown.size() * 8, hipMemcpyHostToDevice));
-        c->h_nn_off.swap(nn_off);
         HIP_TRY(dalloc(&c->d_nn_off, G)); HIP_TRY(dalloc(&c->d_nn_since, G)); HIP_TRY(dalloc(&c->d_nn_out, G));
-        HIP_TRY(dalloc(&c->d_nn_list, std::max<uint32_t>(c->h_nn_off[G], 1)));
-        if (G) HIP_TRY(hipMemcpy(c->d_nn_off, c->h_nn_off.data(), (size_t)G * 4, hipMemcpyHostToDevice));
+        HIP_TRY(dalloc(&c->d_nn_list, std::max<uint32_t>(L.list_off[G], 1)));
+        if (G) HIP_TRY(hipMemcpy(c->d_nn_off, L.list_off.data(), (size_t)G * 4, hipMemcpyHostToDevice));
     }
     // host mirrors for node events (table slots up to the capacity)
-    c->pair_next.assign(n_gp, 0);
-    c->pair_end.assign(n_gp, 0);
-    c->pair_lo.assign(n_gp, 0);
-    for (uint32_t q = 0; q < n_gp; ++q) {
-        const uint32_t a = piece_off[pp_off[q]], z = piece_off[pp_off[q + 1]];
-        c->pair_end[q] = z;
-        c->pair_lo[q] = a;
-        c->pair_next[q] = a + (uint32_t)pair_cnt[q];
-    }
+    commit_layout(c, L, pk_ok);
     c->h_e_node.swap(e_node);
     c->h_e_node.resize(E);
     c->ne_off.swap(ne_off);
@@ -2228,13 +2174,6 @@ int32_t esc_load_nodes(esc_ctx* c, const esc_node_soa* s, int64_t lo, int64_t hi
         c->q_bounds[r] = a;
     }
     c->pair_live = pair_cnt;
-    c->h_gn.clear();
-    c->n_entries = E;
-    c->n_pieces = n_pieces;
-    c->n_spans = (int64_t)span_off.size() - 1;
-    c->pc_lo = pc_lo;
-    c->pc_hi = pc_hi;
-    c->node_bytes = node_bytes;
     c->n_nodes = n;
     c->n_xl = s->n_xl;
     c->n_trk = s->n_trk;
@@ -2258,8 +2197,7 @@ int32_t esc_stream_bytes(const esc_ctx* c, int64_t* pod_bytes, int64_t* node_byt
     // K1: flags 4 + cpu0 4 + mem0 8 + pair0 4 per pod, 16 per extra container record,
     // 4 per extra pair, 8 per C tile (record offsets); a pod of a packed class 12 B + 8 per
     // record, of a packed small class 8 B + 8 per record + 2 per extra pair (esc_kernels.h,
-    // kp_*, kp8_*); K2:
-    // see esc_load_nodes
+    // kp_*, kp8_*); K2: see plan_node_layout (esc_node_layout.h)
     *pod_bytes = c->live_pods * 20 + c->live_xc * 16 + c->live_xp * 4 + c->c_tiles_loaded * 8 - c->live_pk_pods * 8 -
                  c->live_pk_xc * 8 - c->live_p8_pods * 4 - c->live_p8_xp * 2;
     *node_bytes = c->node_bytes;
@@ -2490,7 +2428,7 @@ int32_t esc_reduce(esc_ctx* c) {
     hipSetDevice(c->device);
     if (c->ng_pending) {                               // the previous reduce was not decided:
         // its node groups consume its tracker sums now (no decisions), so no step's sums mix
-        HIP_TRY(launch_node_groups(group_dev(c), node_dev(c), own_list(c), c->nodes.rows, c->d_trk_acc, c->d_nwords,
+        HIP_TRY(launch_node_groups(group_dev(c), node_dev(c), own_list(c), c->nodes.d.rows, c->d_trk_acc, c->d_nwords,
                                    NGDecide{nullptr, nullptr, nullptr}, c->stream));
     }
     c->ng_pending = true;
@@ -2604,7 +2542,7 @@ int32_t esc_decide(esc_ctx* c) {
         }
     }
 #endif
-    HIP_TRY(launch_node_groups(group_dev(c), node_dev(c), own_list(c), c->nodes.rows, c->d_trk_acc, c->d_nwords,
+    HIP_TRY(launch_node_groups(group_dev(c), node_dev(c), own_list(c), c->nodes.d.rows, c->d_trk_acc, c->d_nwords,
                                NGDecide{c->d_pwords, c->d_dec, c->zero_copy ? c->h_cdec_dev : c->d_cdec, sel_out(c), ng_trace},
                                c->stream));
     c->sel_valid = sel_out(c).out != nullptr;
@@ -3299,11 +3237,11 @@ void entry_patch(esc_ctx* c, Patches& P, uint32_t e, uint32_t f, int64_t cpu, in
 
 PatchTargets node_targets(esc_ctx* c) {
     PatchTargets t{};
-    t.u32[NT_FLAGS] = c->nodes.flags; t.u32[NT_EFLAGS] = c->nodes.e_flags; t.u32[NT_LABEL0] = c->nodes.label0;
-    t.u32[NT_XLOFF] = c->nodes.xl_off; t.u32[NT_ENODE] = c->nodes.e_node; t.u32[NT_XL] = c->nodes.xl;
+    t.u32[NT_FLAGS] = c->nodes.flags; t.u32[NT_EFLAGS] = c->nodes.d.e_flags; t.u32[NT_LABEL0] = c->nodes.label0;
+    t.u32[NT_XLOFF] = c->nodes.d.xl_off; t.u32[NT_ENODE] = c->nodes.d.e_node; t.u32[NT_XL] = c->nodes.d.xl;
     t.i64[NT_CPU - 6] = c->nodes.cpu; t.i64[NT_MEM - 6] = c->nodes.mem;
-    t.i64[NT_ECPU - 6] = c->nodes.e_cpu; t.i64[NT_EMEM - 6] = c->nodes.e_mem;
-    t.i64[NT_EPK - 6] = reinterpret_cast<int64_t*>(c->nodes.e_pk);
+    t.i64[NT_ECPU - 6] = c->nodes.d.e_cpu; t.i64[NT_EMEM - 6] = c->nodes.d.e_mem;
+    t.i64[NT_EPK - 6] = reinterpret_cast<int64_t*>(c->nodes.d.e_pk);
     t.i64[NT_CREATED - 6] = c->nodes.created;
     return t;
 }
@@ -3446,7 +3384,7 @@ int32_t patch_nodes(esc_ctx* c, const std::vector<int64_t>& ids) {
     int32_t rc = apply_patches(c, P, {node_targets(c)});
     if (rc) return rc;
     if (first_changed)
-        HIP_TRY(hipMemcpy(c->nodes.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->nodes.d.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
     rc = patch_regions(c, ids);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3477,7 +3415,7 @@ int32_t write_tracker(esc_ctx* c, std::vector<uint64_t>& next) {
         HIP_TRY(hipMemcpy(b.trk_node, tn.data(), nt * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b.trk_group, tg.data(), nt * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMemcpy(b.trk_start, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b.d.trk_start, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
     c->h_trk.swap(next);
     c->n_trk = nt;
     drop_graphs(c);
@@ -3953,7 +3891,7 @@ int32_t esc_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out) {
         int32_t rc = apply_patches(c, P, {node_targets(c)});
         if (rc) return rc;
         if (first_changed)
-            HIP_TRY(hipMemcpy(c->nodes.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(c->nodes.d.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
         for (int64_t i = 0; i < n; ++i) c->h_created.push_back(s->created_ns[i]);
         c->node_hi = c->n_nodes;
         if (k5) {
@@ -4019,7 +3957,7 @@ int32_t esc_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n) {
             first_changed = true;
         }
         if (first_changed)
-            HIP_TRY(hipMemcpy(c->nodes.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(c->nodes.d.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
         // the placement stays: a deleted node's entries are absent (K6 / K7 skip them) and its
         // pods' PodRefs stay in its run until they are rebound or deleted
         c->rm_valid = c->nn_valid = false;
@@ -4299,7 +4237,7 @@ int32_t relabel_apply(esc_ctx* c, const int64_t* ids, const esc_node_soa* s, con
     // allNodes[0] of the groups whose pair gained or lost a node
     for (int32_t g = 0; g < c->gi.G; ++g)
         if (pair_touched[c->gi.gpair[g]]) pair_first(c, c->gi.gpair[g], c->h_gnode[g]);
-    HIP_TRY(hipMemcpy(c->nodes.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->nodes.d.gnode, c->h_gnode.data(), c->h_gnode.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
     if (int32_t rc = apply_patches(c, P, {node_targets(c)})) return rc;
     // K5: memberships join their regions at their (new) place
     if (k5) {
@@ -4464,10 +4402,10 @@ int32_t esc_load_placement(esc_ctx* c, const uint32_t* pod_node, const int64_t* 
         HIP_TRY(dalloc(&c->d_rm_out, G)); HIP_TRY(dalloc(&c->d_rm_off, G));
         // each group's deletable-node list can hold all of its pair's entries
         std::vector<uint32_t> poff(c->n_pieces + 1), ppo(c->gi.n_gp + 1), ppair(std::max<int64_t>(c->n_pieces, 1));
-        HIP_TRY(hipMemcpy(poff.data(), c->nodes.piece_off, poff.size() * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ppo.data(), c->nodes.pp_off, ppo.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(poff.data(), c->nodes.d.piece_off, poff.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ppo.data(), c->nodes.d.pp_off, ppo.size() * 4, hipMemcpyDeviceToHost));
         if (c->n_pieces)
-            HIP_TRY(hipMemcpy(ppair.data(), c->nodes.piece_pair, c->n_pieces * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(ppair.data(), c->nodes.d.piece_pair, c->n_pieces * 4, hipMemcpyDeviceToHost));
         std::vector<uint32_t> epair(std::max<int64_t>(c->n_entries, 1), NONE);
         for (int64_t pc = 0; pc < c->n_pieces; ++pc)
             for (uint32_t e = poff[pc]; e < poff[pc + 1]; ++e) epair[e] = ppair[pc];
@@ -4794,7 +4732,7 @@ namespace {
 // context's, so whatever this holds when it goes out of scope — the new buffers of a rebuild
 // that failed, the old ones of one that succeeded, the scratch of both — is released.
 struct RebuildBufs {
-    NodeBuf nb;                                   // entries, pieces, spans, rows, gnode, xl, xl_off, trk_start
+    NodeDerived nb;                               // entries, pieces, spans, rows, gnode, xl, xl_off, trk_start
     uint32_t *ne_off = nullptr, *ne_pos = nullptr, *e_pair = nullptr, *occ = nullptr, *occ_local = nullptr;
     uint32_t *nn_off = nullptr, *nn_list = nullptr, *rm_off = nullptr, *rm_list = nullptr;
     uint8_t* blob = nullptr;                      // the staged layout tables
@@ -4863,77 +4801,31 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
         const uint32_t nx = nf_xlbl(nflags[i]);
         std::copy_n(c->h_xl.begin() + c->h_xl_off[i], nx, h_xl.begin() + xl_off[i]);
     }
-    const int64_t xl_cap = (int64_t)xw + (sf > 0 ? (int64_t)std::ceil((double)xw * sf) + 256 : 0);
-    // group pairs: live entries sorted by node, then ceil(live * f) + 4 spare ones; the
-    // entries of pairs no group selects follow all of them
-    std::vector<uint32_t> start((size_t)n_gp + 1), pair_lo(n_gp), pair_next(n_gp), pair_end(n_gp);
-    uint64_t s_acc = 0, e_acc = 0;
+    const int64_t xl_cap = label_words((int64_t)xw, sf);
+    // group pairs: live entries sorted by node (start: where a pair's begin among the sorted
+    // elements), then their spare ones; the entries of pairs no group selects follow all of
+    // them as one run (pair NONE: nothing reads a piece of such a pair).  This rank's share
+    // stays inside the kept owner bounds.  The ranges, pieces, spans and list offsets are
+    // plan_node_layout's (esc_node_layout.h), as at a load.
+    std::vector<uint32_t> start((size_t)n_gp + 1);
+    uint64_t s_acc = 0;
     for (uint32_t q = 0; q < n_gp; ++q) {
-        const int64_t live = c->pair_live[q];
-        if (live < 0) return fail_hip(hipErrorUnknown, "nodes rebuild: pair mirror");
-        const int64_t sp = sf > 0 ? (int64_t)std::ceil((double)live * sf) + 4 : 0;
+        if (c->pair_live[q] < 0) return fail_hip(hipErrorUnknown, "nodes rebuild: pair mirror");
         start[q] = (uint32_t)s_acc;
-        pair_lo[q] = (uint32_t)e_acc;
-        s_acc += (uint64_t)live;
-        e_acc += (uint64_t)(live + sp);
-        if (e_acc >= 0xFFFFFFFFull) return ESC_E_LIMIT;
-        pair_next[q] = pair_lo[q] + (uint32_t)live;
-        pair_end[q] = (uint32_t)e_acc;
+        s_acc += (uint64_t)c->pair_live[q];
     }
     start[n_gp] = (uint32_t)s_acc;
     if ((int64_t)s_acc > M) return fail_hip(hipErrorUnknown, "nodes rebuild: pair mirror");
-    const uint64_t spare_total = e_acc - s_acc;
-    const int64_t E = M + (int64_t)spare_total;
-    if (E >= (int64_t)0xFFFFFFFF) return ESC_E_LIMIT;
-    // pieces: runs of one pair that cross no multiple of PIECE_ALIGN (as esc_load_nodes cuts
-    // them); the entries behind the group pairs are cut at the alignment alone (pair NONE:
-    // nothing reads a piece of a pair no group selects)
-    std::vector<uint32_t> piece_off, piece_pair, pp_off((size_t)n_gp + 1);
-    auto cut = [&](uint64_t a, uint64_t z, uint32_t q) {
-        while (a < z) {
-            piece_off.push_back((uint32_t)a);
-            piece_pair.push_back(q);
-            a = std::min<uint64_t>(z, (a / PIECE_ALIGN + 1) * PIECE_ALIGN);
-        }
-    };
-    for (uint32_t q = 0; q < n_gp; ++q) {
-        pp_off[q] = (uint32_t)piece_pair.size();
-        cut(pair_lo[q], pair_end[q], q);
-    }
-    pp_off[n_gp] = (uint32_t)piece_pair.size();
-    cut(e_acc, (uint64_t)E, NONE);
-    const int64_t n_pieces = (int64_t)piece_pair.size();
-    piece_off.push_back((uint32_t)E);
-    // this rank's share inside the kept owner bounds, K2's bytes and spans (as esc_load_nodes)
-    const int64_t pc_lo = pp_off[c->q_lo], pc_hi = pp_off[c->q_hi];
-    const int64_t per_entry = pk_ok ? 16 : 20;
-    int64_t node_bytes = 0;
-    for (int64_t p = pc_lo; p < pc_hi; ++p) node_bytes += 8 + per_entry * (int64_t)(piece_off[p + 1] - piece_off[p]);
-    std::vector<uint32_t> span_off(1, (uint32_t)pc_lo);
-    {
-        int64_t acc = 0, np = 0;
-        for (int64_t p = pc_lo; p < pc_hi; ++p) {
-            const int64_t len = (int64_t)piece_off[p + 1] - piece_off[p];
-            if (acc > 0 && (acc + len > NODE_SPAN || np == 63)) { span_off.push_back((uint32_t)p); acc = 0; np = 0; }
-            acc += len;
-            ++np;
-        }
-        if (pc_hi > pc_lo) span_off.push_back((uint32_t)pc_hi);
-    }
-    std::vector<uint32_t> span_e(span_off.size());
-    for (size_t w = 0; w < span_off.size(); ++w) span_e[w] = piece_off[span_off[w]];
-    // a group's new-node and removal lists hold at most its pair's entry capacity
-    std::vector<uint32_t> list_off((size_t)G + 1, 0);
-    for (int32_t g = 0; g < G; ++g) {
-        const uint32_t q = c->gi.gpair[g];
-        const uint64_t end = (uint64_t)list_off[g] + (pair_end[q] - pair_lo[q]);
-        if (end >= 0xFFFFFFFFull) return ESC_E_LIMIT;
-        list_off[g + 1] = (uint32_t)end;
-    }
+    NodeLayout L;
+    if (const int32_t rc = plan_node_layout(L, c->pair_live, sf, {TailRun{NONE, (uint64_t)M - s_acc}}, c->q_lo, c->q_hi,
+                                            pk_ok, c->gi.gpair.data(), G))
+        return rc;
+    const int64_t E = L.n_entries, n_pieces = L.n_pieces;
+    const uint64_t spare_total = (uint64_t)(E - M);
     // ---- one staged copy of every table (the error word, zero, at its end)
     struct Part { const std::vector<uint32_t>* v; size_t at; };
-    Part parts[] = {{&ne_off, 0}, {&xl_off, 0}, {&trk_start, 0}, {&start, 0}, {&pair_lo, 0}, {&piece_off, 0},
-                    {&piece_pair, 0}, {&pp_off, 0}, {&span_off, 0}, {&span_e, 0}, {&list_off, 0}};
+    Part parts[] = {{&ne_off, 0}, {&xl_off, 0}, {&trk_start, 0}, {&start, 0}, {&L.pair_lo, 0}, {&L.piece_off, 0},
+                    {&L.piece_pair, 0}, {&L.pp_off, 0}, {&L.span_off, 0}, {&L.span_e, 0}, {&L.list_off, 0}};
     enum { P_NE, P_XLO, P_TRK, P_START, P_LO, P_POFF, P_PPAIR, P_PP, P_SOFF, P_SE, P_LIST, P_N };
     size_t bytes = 0;
     for (Part& p : parts) { p.at = bytes; bytes += (p.v->size() * 4 + 255) & ~(size_t)255; }
@@ -4946,24 +4838,24 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
     t0 = rebuild_clock();
     // ---- the new buffers, beside the resident ones
     RebuildBufs B;
-    NodeBuf& b = B.nb;
+    NodeDerived& b = B.nb;
     const size_t Ez = (size_t)std::max<int64_t>(E, 1), Pz = (size_t)std::max<int64_t>(n_pieces, 1);
     const bool reap = c->d_e_pair != nullptr;     // esc_load_placement's per-entry buffers exist
     HIP_TRY(dalloc(&B.blob, bytes));
     HIP_TRY(dalloc(&b.e_flags, Ez)); HIP_TRY(dalloc(&b.e_node, Ez)); HIP_TRY(dalloc(&b.e_cpu, Ez));
     HIP_TRY(dalloc(&b.e_mem, Ez)); HIP_TRY(dalloc(&b.e_pk, Ez));
-    HIP_TRY(dalloc(&b.piece_off, piece_off.size())); HIP_TRY(dalloc(&b.piece_pair, Pz));
-    HIP_TRY(dalloc(&b.pp_off, pp_off.size())); HIP_TRY(dalloc(&b.span_off, span_off.size()));
-    HIP_TRY(dalloc(&b.span_e, span_e.size())); HIP_TRY(dalloc(&b.rows, Pz * NR_K));
+    HIP_TRY(dalloc(&b.piece_off, L.piece_off.size())); HIP_TRY(dalloc(&b.piece_pair, Pz));
+    HIP_TRY(dalloc(&b.pp_off, L.pp_off.size())); HIP_TRY(dalloc(&b.span_off, L.span_off.size()));
+    HIP_TRY(dalloc(&b.span_e, L.span_e.size())); HIP_TRY(dalloc(&b.rows, Pz * NR_K));
     HIP_TRY(dalloc(&b.gnode, (size_t)G));
     HIP_TRY(dalloc(&b.xl, (size_t)xl_cap)); HIP_TRY(dalloc(&b.xl_off, xl_off.size()));
     HIP_TRY(dalloc(&b.trk_start, trk_start.size()));
     HIP_TRY(dalloc(&B.ne_off, ne_off.size())); HIP_TRY(dalloc(&B.ne_pos, Ez));
-    HIP_TRY(dalloc(&B.nn_off, (size_t)G)); HIP_TRY(dalloc(&B.nn_list, std::max<uint32_t>(list_off[G], 1)));
+    HIP_TRY(dalloc(&B.nn_off, (size_t)G)); HIP_TRY(dalloc(&B.nn_list, std::max<uint32_t>(L.list_off[G], 1)));
     if (reap) {
         HIP_TRY(dalloc(&B.e_pair, Ez)); HIP_TRY(dalloc(&B.occ, 2 * Ez));
         if (c->d_occ_local) HIP_TRY(dalloc(&B.occ_local, 2 * Ez));
-        HIP_TRY(dalloc(&B.rm_off, (size_t)G)); HIP_TRY(dalloc(&B.rm_list, std::max<uint32_t>(list_off[G], 1)));
+        HIP_TRY(dalloc(&B.rm_off, (size_t)G)); HIP_TRY(dalloc(&B.rm_list, std::max<uint32_t>(L.list_off[G], 1)));
     }
     HIP_TRY(dalloc(&B.elems[0], (size_t)M)); HIP_TRY(dalloc(&B.elems[1], (size_t)M));
     HIP_TRY(dalloc(&B.hist, std::max(sort_hist_words(std::max<int64_t>(M, 1)), sort_hist_words(1) * 4)));
@@ -4975,9 +4867,9 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
         return words ? hipMemcpyAsync(dst, view(k), words * 4, hipMemcpyDeviceToDevice, st) : hipSuccess;
     };
     HIP_TRY(keep(B.ne_off, P_NE, ne_off.size())); HIP_TRY(keep(b.xl_off, P_XLO, xl_off.size()));
-    HIP_TRY(keep(b.trk_start, P_TRK, trk_start.size())); HIP_TRY(keep(b.piece_off, P_POFF, piece_off.size()));
-    HIP_TRY(keep(b.piece_pair, P_PPAIR, piece_pair.size())); HIP_TRY(keep(b.pp_off, P_PP, pp_off.size()));
-    HIP_TRY(keep(b.span_off, P_SOFF, span_off.size())); HIP_TRY(keep(b.span_e, P_SE, span_e.size()));
+    HIP_TRY(keep(b.trk_start, P_TRK, trk_start.size())); HIP_TRY(keep(b.piece_off, P_POFF, L.piece_off.size()));
+    HIP_TRY(keep(b.piece_pair, P_PPAIR, L.piece_pair.size())); HIP_TRY(keep(b.pp_off, P_PP, L.pp_off.size()));
+    HIP_TRY(keep(b.span_off, P_SOFF, L.span_off.size())); HIP_TRY(keep(b.span_e, P_SE, L.span_e.size()));
     HIP_TRY(keep(B.nn_off, P_LIST, (size_t)G));
     if (reap) HIP_TRY(keep(B.rm_off, P_LIST, (size_t)G));
 #if ESC_MEASURE
@@ -4987,7 +4879,7 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
 #endif
     // ---- list, sort, place
     RebuildDev R{};
-    R.flags = c->nodes.flags; R.label0 = c->nodes.label0; R.xl_off = c->nodes.xl_off; R.xl = c->nodes.xl;
+    R.flags = c->nodes.flags; R.label0 = c->nodes.label0; R.xl_off = c->nodes.d.xl_off; R.xl = c->nodes.d.xl;
     R.cpu = c->nodes.cpu; R.mem = c->nodes.mem;
     R.n_cap = NC; R.xl_len = c->xl_used;
     R.ne_off = view(P_NE); R.xl_off_new = view(P_XLO); R.trk_start = view(P_TRK); R.start = view(P_START);
@@ -5014,36 +4906,25 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
     std::vector<GroupNode> gn((size_t)G);
     for (int32_t g = 0; g < G; ++g) {
         const uint32_t q = c->gi.gpair[g];
-        GroupNode& x = gn[g];
-        x.plo = std::max<int64_t>(pp_off[q], pc_lo);
-        x.phi = std::min<int64_t>(pp_off[q + 1], pc_hi);
-        if (x.phi < x.plo) x.phi = x.plo;
-        const bool any = pair_next[q] > pair_lo[q];
-        x.first = any ? (int64_t)h_e_node[pair_lo[q]] : INT64_MAX;      // sorted by node: the lowest
-        if (any && (x.first < 0 || x.first >= N)) return fail_hip(hipErrorUnknown, "nodes rebuild: entry mirror");
-        x.first_cpu = any ? c->h_ncpu[x.first] : 0;
-        x.first_mem = any ? c->h_nmem[x.first] : 0;
+        const bool any = L.pair_next[q] > L.pair_lo[q];
+        const uint32_t first = any ? h_e_node[L.pair_lo[q]] : NONE;      // sorted by node: the lowest
+        if (any && (int64_t)first >= N) return fail_hip(hipErrorUnknown, "nodes rebuild: entry mirror");
+        gn[g] = group_node(L, q, first, any ? c->h_ncpu[first] : 0, any ? c->h_nmem[first] : 0);
     }
     if (G) HIP_TRY(hipMemcpy(b.gnode, gn.data(), gn.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
     g_rebuild_ms[3] = (rebuild_clock() - t0) * 1e3;
     // ---- the swap: nothing below fails before the snapshot is whole again
     drop_graphs(c);                                          // captured steps hold the old buffers
-    NodeBuf& o = c->nodes;
-    std::swap(o.e_flags, b.e_flags); std::swap(o.e_node, b.e_node); std::swap(o.e_cpu, b.e_cpu);
-    std::swap(o.e_mem, b.e_mem); std::swap(o.e_pk, b.e_pk); std::swap(o.piece_off, b.piece_off);
-    std::swap(o.piece_pair, b.piece_pair); std::swap(o.pp_off, b.pp_off); std::swap(o.span_off, b.span_off);
-    std::swap(o.span_e, b.span_e); std::swap(o.rows, b.rows); std::swap(o.gnode, b.gnode);
-    std::swap(o.xl, b.xl); std::swap(o.xl_off, b.xl_off); std::swap(o.trk_start, b.trk_start);
+    std::swap(c->nodes.d, B.nb);
     std::swap(c->d_ne_off, B.ne_off); std::swap(c->d_ne_pos, B.ne_pos);
     std::swap(c->d_nn_off, B.nn_off); std::swap(c->d_nn_list, B.nn_list);
     if (reap) {
         std::swap(c->d_e_pair, B.e_pair); std::swap(c->d_occ, B.occ); std::swap(c->d_occ_local, B.occ_local);
         std::swap(c->d_rm_off, B.rm_off); std::swap(c->d_rm_list, B.rm_list);
-        c->h_rm_off = list_off;
+        c->h_rm_off = L.list_off;
     }
-    c->h_nn_off.swap(list_off);
+    commit_layout(c, L, pk_ok);
     c->h_nn_new.clear();
-    c->pair_lo.swap(pair_lo); c->pair_next.swap(pair_next); c->pair_end.swap(pair_end);
     c->h_e_node.swap(h_e_node);
     ne_off.resize((size_t)N + 1);                            // the host map covers the nodes so far (adds append)
     c->ne_off.swap(ne_off);
@@ -5056,14 +4937,6 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
     c->xl_used = c->n_xl = (int64_t)xw;
     c->xl_cap = xl_cap;
     c->h_gnode.swap(gn);
-    c->h_gn.clear();
-    c->n_entries = E;
-    c->n_pieces = n_pieces;
-    c->n_spans = (int64_t)span_off.size() - 1;
-    c->pc_lo = pc_lo;
-    c->pc_hi = pc_hi;
-    c->node_bytes = node_bytes;
-    c->e_pk_ok = pk_ok;
     c->sel_valid = c->rm_valid = c->nn_valid = false;
     c->sorted = false;
     // ---- what is recounted over the new entries: a failure from here on leaves the node
@@ -5343,15 +5216,15 @@ int32_t esc_debug_poke(esc_ctx* c, int32_t what, int64_t index, int64_t value) {
     switch (what) {
     case 0:
         if (!live_entry(index) || value < 1 || value > 3) return ESC_E_INVAL;
-        HIP_TRY(hipMemcpy(&w, c->nodes.e_flags + index, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&w, c->nodes.d.e_flags + index, 4, hipMemcpyDeviceToHost));
         w ^= (uint32_t)value;
-        HIP_TRY(hipMemcpy(c->nodes.e_flags + index, &w, 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->nodes.d.e_flags + index, &w, 4, hipMemcpyHostToDevice));
         return ESC_OK;
     case 1:
         if (!live_entry(index) || !entry_cpu_packs(value)) return ESC_E_INVAL;
         w = (uint32_t)value;
-        HIP_TRY(hipMemcpy(c->nodes.e_cpu + index, &value, 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(reinterpret_cast<uint32_t*>(c->nodes.e_pk + index) + 1, &w, 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->nodes.d.e_cpu + index, &value, 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(reinterpret_cast<uint32_t*>(c->nodes.d.e_pk + index) + 1, &w, 4, hipMemcpyHostToDevice));
         return ESC_OK;
     case 2:
         if (region_group(index) < 0 || value < 1 || value > 7) return ESC_E_INVAL;
@@ -5387,7 +5260,7 @@ int32_t esc_debug_poke(esc_ctx* c, int32_t what, int64_t index, int64_t value) {
         return ESC_OK;
     case 7:
         if (index >= c->gi.G) return ESC_E_INVAL;
-        HIP_TRY(hipMemcpy(&c->nodes.gnode[index].first_cpu, &value, 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(&c->nodes.d.gnode[index].first_cpu, &value, 8, hipMemcpyHostToDevice));
         return ESC_OK;
     case 8:
         if (index >= c->n_nodes || (c->h_nflags[index] & ESC_NF_ABSENT)) return ESC_E_INVAL;

@@ -17,7 +17,7 @@ contiguous pair ranges balanced by entry count).
 import numpy as np
 
 NODE_PIECE = 1024
-PIECE_ALIGN = 256          # esc_kernels.h: no piece crosses a multiple of it (K2's spans come out full)
+PIECE_ALIGN = 256          # esc_common.h: no piece crosses a multiple of it (K2's spans come out full)
 NONE = 0xFFFFFFFF
 
 
@@ -153,7 +153,7 @@ def node_bytes(nodes: dict, n_gp: int, rank: int = 0, world: int = 1) -> int:
     if E == 0:
         return 0
     # pieces: runs of one pair's entries cut at every multiple of PIECE_ALIGN entries too
-    # (K2's spans come out full, esc_runtime.hip esc_load_nodes), so <= NODE_PIECE long
+    # (K2's spans come out full, esc_node_layout.h plan_node_layout), so <= NODE_PIECE long
     assert NODE_PIECE % PIECE_ALIGN == 0
     starts = np.flatnonzero(np.r_[True, q[1:] != q[:-1]])
     p_start = np.union1d(starts, np.arange(0, E, PIECE_ALIGN))
