@@ -215,6 +215,9 @@ def test_random_objects_vs_literal(esc, seed):
             assert int(d["delta"]) == L["delta"] and int(d["n_to_taint"]) == L["n_to_taint"], (g, L)
             assert _bits(d["cpu_pct"]) == _bits(L["cpu_pct"]) and _bits(d["mem_pct"]) == _bits(L["mem_pct"])
             assert (int(d["cached_cpu_m"]), int(d["cached_mem_b"])) == (L["cached_cpu_m"], L["cached_mem_b"])
+            assert soa.STATUS_ERR[int(d["status"])] == L["err"], (g, L)
+            assert int(d["taint_status"]) == (esc._lib.ESC_ST_ERR_TAINT_MIN if L["taint_err"] is not None
+                                              else esc._lib.ESC_ST_OK), (g, L)
     ctx.force_wide(False)
     ctx.sort_nodes()
     for g in range(G):

@@ -147,7 +147,8 @@ def test_packer_encoding_details():
 
 
 def test_scalar_math_matches_literal():
-    """The library's host build of the decision math (same code as the K4 kernel)."""
+    """The library's host build of the decision math (the same source as the K4 kernel, whose
+    device build tests/test_gpu_decision_table.py checks)."""
     import ctypes as C
     from escalator_amd import _lib as L
     lib = L.load()
