@@ -451,7 +451,7 @@ int32_t add_nodes_parallel(esc_packer* pk, const esc_node_obj* nodes, int64_t n,
 
 }  // namespace
 
-// Implemented in esc_api.hip (needs the ctx layout).
+// Implemented in esc_runtime.hip (needs the ctx layout).
 namespace esc { const GroupIndex* ctx_group_index(const esc_ctx* ctx); }
 
 extern "C" {

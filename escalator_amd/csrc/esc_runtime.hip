@@ -6,30 +6,12 @@
 // and an optional hipGraph of the whole decision step.  The only host<->device
 // traffic per decision is the launch (a graph replay for one rank) and the copy of the
 // per-group decisions back to pinned host memory.
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
+//
+// The device rebuild of the node side and the audit are in esc_rebuild.hip; esc_ctx.h holds
+// the context and what the two files share.
+#include <cstdarg>
 
-#include <algorithm>
-#include <array>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <ctime>
-#include <new>
-#include <thread>
-#include <type_traits>
-#include <string>
-#include <vector>
-
-#include "esc_internal.h"
-#include "esc_kernels.h"
-#include "esc_multi.h"
-#include "esc_node_layout.h"
-
-#ifndef ESC_MEASURE
-#define ESC_MEASURE 0   // 1: the measurement library (Makefile ABLATIONS=1) reads its knobs
-#endif
+#include "esc_ctx.h"
 
 using namespace esc;
 
@@ -38,81 +20,8 @@ namespace {
 constexpr int LDS_BYTES = 160 * 1024;
 constexpr int POD_WINDOW_MAX = LDS_BYTES / 16;      // groups whose pod partials fit in LDS
 static_assert(POD_WINDOW_MAX % 2 == 0 && FC_COL % 2 == 0, "K1's 16-B partial-row stores need even window starts");
-constexpr int MAX_STAGES = 10;
-constexpr int32_t HTOT_MAX_GROUPS = 1024;   // K4 writes the totals records to host memory (<= 104 KB)
-
-#define HIP_TRY(x)                                              \
-    do {                                                        \
-        hipError_t e_ = (x);                                    \
-        if (e_ != hipSuccess) return fail_hip(e_, #x);          \
-    } while (0)
 
 thread_local char g_last_error[256];
-
-template <class T>
-hipError_t dalloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T));
-}
-
-// A device copy of a host vector.
-template <class T>
-hipError_t dcopy(T** p, const std::vector<T>& v) {
-    const hipError_t e = dalloc(p, v.size());
-    return e != hipSuccess || v.empty() ? e : hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
-template <class T>
-void dfree(T*& p) {
-    if (p) hipFree(p);
-    p = nullptr;
-}
-
-struct PodBuf {
-    uint32_t* kb = nullptr;                      // K blocks (tile-major K section)
-    uint32_t *flags = nullptr, *cpu0 = nullptr, *pair0 = nullptr, *xp = nullptr, *xc_base = nullptr,
-             *xp_base = nullptr, *big = nullptr;
-    int64_t *mem0 = nullptr, *xc_cpu = nullptr, *xc_mem = nullptr;
-    PodClass* cls = nullptr;
-    void release() {
-        dfree(kb); dfree(flags); dfree(cpu0); dfree(pair0); dfree(xp); dfree(xc_base); dfree(xp_base); dfree(big);
-        dfree(mem0); dfree(xc_cpu); dfree(xc_mem); dfree(cls);
-    }
-};
-
-// What is derived from the node table and the layout (esc_node_layout.h): the buffers a
-// rebuild builds anew and swaps in as one (esc_nodes_rebuild).
-struct NodeDerived {
-    // pair-major entries, pieces, K2 rows
-    uint32_t *e_flags = nullptr, *e_node = nullptr, *piece_off = nullptr, *piece_pair = nullptr, *pp_off = nullptr;
-    uint32_t* span_off = nullptr;                // K2 waves' piece ranges
-    uint32_t* span_e = nullptr;                  // and their entry ranges
-    int64_t *e_cpu = nullptr, *e_mem = nullptr, *rows = nullptr;
-    uint4* e_pk = nullptr;                       // the entries packed 16 B each (NodeDev::e_pk)
-    GroupNode* gnode = nullptr;
-    // the extra labels (compacted by a rebuild), their offsets and the tracker's per-node index
-    uint32_t *xl = nullptr, *xl_off = nullptr, *trk_start = nullptr;
-    void release() {
-        dfree(gnode);
-        dfree(e_flags); dfree(e_node); dfree(piece_off); dfree(piece_pair); dfree(pp_off); dfree(span_off); dfree(span_e);
-        dfree(e_cpu); dfree(e_mem); dfree(rows); dfree(e_pk);
-        dfree(xl); dfree(xl_off); dfree(trk_start);
-    }
-};
-
-struct NodeBuf {
-    // node table (snapshot order), tracker by (node, group)
-    uint32_t *flags = nullptr, *label0 = nullptr;
-    int64_t *cpu = nullptr, *mem = nullptr, *created = nullptr;
-    int32_t *trk_node = nullptr, *trk_group = nullptr;
-    NodeDerived d;
-    void release() {
-        dfree(flags); dfree(label0); dfree(cpu); dfree(mem);
-        dfree(created); dfree(trk_node); dfree(trk_group);
-        d.release();
-    }
-};
 
 }  // namespace
 
@@ -125,6 +34,14 @@ int32_t fail_hip(hipError_t e, const char* what) {
 int32_t fail_comm(const char* what, const char* why) {
     std::snprintf(g_last_error, sizeof g_last_error, "%s: %s", what, why);
     return ESC_E_COMM;
+}
+
+int32_t fail_fmt(int32_t code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(g_last_error, sizeof g_last_error, fmt, ap);
+    va_end(ap);
+    return code;
 }
 
 const RcclApi& rccl() {
@@ -155,334 +72,12 @@ const RcclApi& rccl() {
 }
 }  // namespace esc
 
-namespace {
-
-int bit_width(uint64_t v) {
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
-}
-
-}  // namespace
-
-struct esc_ctx {
-    int device = -1, rank = 0, world = 1;
-    bool has_device = false;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int cu_count = 0;
-    GroupIndex gi;
-    std::vector<GroupParams> params;
-    // device group tables
-    uint8_t* d_dry = nullptr;
-    GroupParams* d_params = nullptr;
-    uint32_t *d_gpair = nullptr, *d_node_code = nullptr, *d_code_list = nullptr;
-    uint32_t* d_gslot = nullptr;
-    // snapshot
-    std::vector<PodBuf> pods;
-    int n_replicas = 1, cur = 0;
-    int64_t k_weight = 0;
-    int64_t n_pods = 0, k_tiles = 0, c_tiles = 0, n_xc = 0, n_xp = 0, pod_offset = 0, n_big = 0;
-    int32_t n_cls = 0;
-    bool pods_loaded = false;
-    NodeBuf nodes;
-    int64_t n_nodes = 0, n_xl = 0, n_trk = 0, node_lo = 0, node_hi = 0;
-    int64_t n_entries = 0, n_pieces = 0, pc_lo = 0, pc_hi = 0, node_bytes = 0, n_spans = 0;
-    int64_t ts_min = 0, ts_max = 0;
-    bool nodes_loaded = false;
-    // every node's allocatable cpu is in [0, 2^32): K2 reads the packed 16-B entries (node
-    // events that break it switch K2 back to the three entry arrays, dropping the graphs)
-    bool e_pk_ok = false;
-    uint32_t q_lo = 0, q_hi = 0;                              // the group pairs this rank owns (§7)
-    std::vector<uint32_t> q_bounds;                           // every rank's first owned pair, + n_gp
-    std::vector<int64_t> pair_live;                           // group pair -> live node entries
-    // work
-    int nblk = 0;
-    uint64_t* d_pod_part = nullptr;
-    uint32_t *d_col_off = nullptr, *d_col_groups = nullptr;   // K3: groups by pod slot column
-    int k3_ablate = 0;                                        // ESC_K3_ABLATE (timing-only knob)
-    bool tail_trace = false;                                  // ESC_TAIL_TRACE (measurement library)
-    uint64_t* d_ttrace = nullptr;                             // tail + node-groups block timestamps
-    int64_t ttrace_cap = 0, ttrace_tail = 0, ttrace_ng = 0;   // words; blocks of the last traced step
-    int64_t* d_wide_pod = nullptr;
-    int64_t* d_k1seg = nullptr;                               // K1 work plan [nblk][K1_SEGS][2]
-    // Compact K1 flush: the pod-slot columns each workgroup's share touches
-    // (bitmap of touch_tw u32 per workgroup, kept current by pod upserts), as per-workgroup
-    // {column, entry} lists and per-column entry ranges on the device.
-    bool touch_on = false;
-    bool full_flush = false;                                  // ESC_K1_FULL_FLUSH=1 (measurement knob)
-    int touch_tw = 0;
-    std::vector<uint32_t> h_touch;
-    std::vector<std::array<int64_t, 3>> h_tile_wg;            // {first tile, end tile, workgroup}, sorted
-    uint32_t* d_touch = nullptr;
-    uint2* d_wg_cols = nullptr;
-    uint32_t* d_wg_off = nullptr;
-    uint32_t* d_col_rows = nullptr;
-    std::vector<double> k1_share;                             // calibrated K1 shares (esc_k1_calibrate)
-    uint64_t* d_k1_trace = nullptr;                           // K1 per-workgroup timestamps (esc_k1_trace)
-    int64_t* d_trk_acc = nullptr;                             // [G][TA_K] dry-mode tracked sums
-    int64_t* d_pwords = nullptr;                              // active exchange buffer [world * own_cap][PW_K]
-    int64_t* own_pwords = nullptr;                            // the context-owned one
-    int64_t* d_nwords = nullptr;                              // [G][NW_K] node words (exact for owned groups),
-                                                              // right after own_pwords (one allocation)
-    // Owner-major exchange rows: group g's pod words at row h_xs[g] = owner *
-    // own_cap + its index among the owner's groups, so one ncclReduceScatter hands every
-    // owner the exact sums of its own groups; h_own = this rank's groups (ascending).
-    int32_t own_cap = 0, own_first = 0;
-    bool own_seq = true;                                      // h_own is own_first + i
-    std::vector<uint32_t> h_own, h_xs;
-    uint32_t *d_own = nullptr, *d_xs = nullptr;
-    esc_group_decision* d_dec = nullptr;                     // full records (device)
-    DecCompact* d_cdec = nullptr;                             // compact records (device; no zero-copy)
-    DecCompact* h_cdec = nullptr;                             // compact records (pinned host)
-    DecCompact* h_cdec_dev = nullptr;                         // device view of h_cdec (zero-copy)
-    bool zero_copy = true;                                    // K3/K4 write compact decisions to h_cdec
-    bool order_in_step = false;                               // K5 ordering inside every decision
-    // selections delivered with the decision (esc_set_selections, SelOut): K4 writes every
-    // decided group's taint / untaint nodes into h_sel (pinned, zero-copy) as [header, nodes]
-    // runs, their offsets into the compact records
-    int32_t sel_slack = -1, sel_group_cap = 0;
-    uint32_t *h_sel = nullptr, *h_sel_dev = nullptr;
-    int64_t sel_words = 0;
-    // the last decision enqueued was given a selection target (sel_out): esc_selections reads
-    // h_cdec[].sel / h_sel only then.  Cleared by everything that changes or drops the target
-    // (esc_set_selections, esc_set_order_in_step, release_sort) and when h_cdec is allocated.
-    bool sel_valid = false;
-    bool want_metrics = false;                                // K4 also writes the gauges
-    esc_group_metrics* d_metrics = nullptr;
-    int64_t* bound_pwords = nullptr;                          // caller-bound exchange buffer
-    int64_t bound_words = 0;                                  // its size: xw_count when bound
-    void* comm = nullptr;                                     // RCCL communicator (esc_comm_init)
-    bool work_ready = false;
-    // An informer-event batch that failed after its first write (a HIP error mid-apply)
-    // leaves host mirrors and device arrays half-updated: decisions and reaping are refused
-    // (ESC_E_STATE) until the snapshot is reloaded (STALE_PODS: esc_load_pods, STALE_NODES:
-    // esc_load_nodes).  ADVICE r4.
-    uint32_t stale = 0;
-    // world > 1: a shard step's node groups run with K4 after the exchange (esc_decide); a
-    // reduce not followed by a decide leaves them pending (the tail's tracker sums unread)
-    bool ng_pending = false;
-    bool force_wide = false;
-    int k1_variant = 0;                                       // ESC_K1_VARIANT (measurement knob)
-    // K pods of a class are laid out in order of pair0 / pod_sort (0: input order), so that a
-    // K1 workgroup's share touches few pod-slot columns; ESC_POD_SORT
-    uint32_t pod_sort = FC_COL;   // one K3 column per bucket (exact pair order serialises K1's LDS atomics: 0.65 ms)
-    // graph
-    bool use_graph = false;
-    std::vector<hipGraphExec_t> graphs;                       // esc_run: whole decision (world 1)
-    std::vector<hipGraphExec_t> rgraphs;                      // esc_reduce: the shard's step (world > 1)
-    // timing
-    bool timing = false;
-    hipEvent_t ev[MAX_STAGES] = {};
-    hipEvent_t k1t_ev[2] = {};                                // esc_k1_time's own pair (stage events stay readable)
-    double stage_ms[MAX_STAGES] = {};
-    int n_stage_ev = 0;
-    bool pending = false;
-    // K5 ordering: the age index (built at load) and the per-decision partition
-    uint64_t* d_mkeys[2] = {nullptr, nullptr};               // index build: (group | creation offset)
-    uint32_t* d_mvals[2] = {nullptr, nullptr};               //              (node | flags << 28)
-    int64_t mcap = 0;                                         // their capacity (memberships)
-    bool age_built = false;
-    bool age_ok = false;                                      // the last build succeeded (its regions are valid)
-    uint32_t *d_hist = nullptr, *d_tot = nullptr;
-    // The index's small tables live in ONE allocation, filled by ONE upload per build
-    // (build_age_index): sorted starts d_seg, region starts / lengths, chunk tables, the
-    // listing's status words, the error word and listed total, the groups' tie flags.
-    uint8_t* d_itab = nullptr;
-    size_t itab_cap = 0;
-    uint32_t *d_total = nullptr, *d_ierr = nullptr;           // (views into d_itab)
-    uint32_t* d_g_tie = nullptr;                              // [G] equal creation times in the group (RegionSink::tie)
-    uint64_t* d_lstat = nullptr;                              // single-pass listing status words
-    int64_t* d_seg = nullptr;
-    int64_t n_memb = 0;
-    int order_src = 0;
-    // group order of the memberships (per-decision 3-way split by class inside each group)
-    uint32_t* d_g_memb = nullptr;                             // K5 regions: membership words
-    uint32_t *d_grp_off = nullptr, *d_gch_off = nullptr;
-    uint64_t* d_ostat = nullptr;                              // k_ord_split status words (x2)
-    int ord_parity = 0;                                       // which status array the next ordering uses
-    // A look-back that gave up (k_ord_split, OrdFail) sets the pinned word h_oerr; the host
-    // reads it after its stream waits: esc_sync reports it once as ESC_E_ORDER and clears it,
-    // and esc_group_order refuses (ESC_E_ORDER) until the next ordering is enqueued.
-    uint32_t *h_oerr = nullptr, *h_oerr_dev = nullptr;
-    bool ord_failed = false;
-    // fault injection, measurement library only (esc_debug_*: tests/test_gpu_faults.py): the
-    // next n ordering / listing launches give up their look-back at once, the next n event
-    // patch applications fail after their host-side writes
-    int lb_fail_order = 0, lb_fail_list = 0, fail_patches = 0;
-    uint32_t *d_pstart = nullptr, *d_plen = nullptr;
-    uint32_t* d_ord = nullptr;                                // K5 output, in the group regions
-    OrdChunk* d_pchunks = nullptr;                            // packed chunks of small groups
-    int64_t n_pchunks = 0, n_psmall = 0;                      // all / those <= ORD_PCHUNK (first)
-    std::vector<uint32_t> h_pstart, h_plen;                   // group regions: start, memberships
-    std::vector<uint32_t> h_pcap;                             // every group's region capacity (owned or not)
-    std::vector<uint32_t> h_gch_off;                          // group -> its split chunks (big groups)
-    int64_t n_gpad = 0;                                       // padded group-order length
-    OrdChunk* d_chunks = nullptr;
-    int64_t n_chunks = 0;
-    uint64_t sort_div = 1;
-    int sort_R = 1;
-    bool age_exact = false;                                   // this snapshot needs the exact 64-bit keys
-    bool sorted = false;
-    std::vector<int64_t> h_created;                           // [lo, hi) creation times (tie order)
-    // node informer events (§8f rank 1): capacity and host mirrors for in-place add / delete
-    int64_t n_cap = 0, xl_used = 0, xl_cap = 0, age_n = -1;
-    std::vector<uint32_t> h_label0, h_xl_off, h_xl;           // node labels (pair ids)
-    std::vector<uint32_t> h_e_node;                           // pair-major entry -> node (NONE: spare)
-    std::vector<uint32_t> pair_next, pair_end;                // group pair -> next spare entry, range end
-    std::vector<uint32_t> pair_lo;                            // group pair -> its first entry
-    std::vector<uint32_t> h_gn;                               // group regions' nodes (lazy mirror of d_g_memb)
-    // per-function drop-ins: the list reducer (esc_list.hip); esc_order_by_creation runs
-    // on a one-group list context
-    esc_ctx* list_ctx = nullptr;
-    esc::ListReducer* lred = nullptr;
-    // single-process multi-device context (esc_ctx_create_multi): every call dispatches to
-    // its per-device contexts (esc_multi.hip); null for a per-device context
-    esc::esc_multi_state* multi = nullptr;
-    // incremental snapshot (§8f rank 1): where each loaded pod lives, free K slots
-    double spare_frac = 0.0;                                  // esc_set_spare
-    hvec<int32_t> pod_cls;                                    // by pod id: K class index, -1 C, -2 absent
-    hvec<int64_t> pod_pos;                                    // K: position in its class; C: base-array index
-    std::vector<std::vector<int64_t>> cls_free;               // per K class: free positions
-    std::vector<PodClass> h_cls;
-    std::vector<int> h_cls_of;                                // signature id -> class index (-1: none)
-    std::vector<uint32_t> h_cflags;                           // C-section flags (deletes keep the counts)
-    std::vector<int64_t> c_free;                              // free C slots (C-array index), room in h_cflags
-    std::vector<uint32_t> h_cused;                            // a C slot's pod's own records | pairs << 16
-    std::vector<uint32_t> h_xc_base, h_xp_base;               // C tiles' record / pair offsets
-    int64_t live_pods = 0, live_xc = 0, live_xp = 0;
-    int64_t live_pk_pods = 0, live_pk_xc = 0;   // of them in packed K classes (either size)
-    int64_t live_p8_pods = 0, live_p8_xp = 0;   // of them in packed small K classes, their extra pairs
-    int64_t c_tiles_loaded = 0;                 // C tiles of loaded pods (the spare C tiles excluded)
-    // node state mirrors for esc_nodes_update
-    std::vector<uint32_t> h_nflags;
-    std::vector<int64_t> h_ncpu, h_nmem;
-    std::vector<uint32_t> ne_off, ne_pos;                     // node -> its pair-major entry positions
-    // The reaping occupancy words, maintained by pod / node events once esc_load_placement
-    // counted them (K6 no longer runs per call): d_occ at one rank; with several ranks the
-    // maintained local words are d_occ_local and d_occ is the exchange buffer.
-    uint32_t* d_occ_local = nullptr;
-    uint32_t* d_ne_off = nullptr;                             // device copies of ne_off / ne_pos
-    uint32_t* d_ne_pos = nullptr;
-    int64_t ne_dev_nodes = -1, ne_dev_pos = -1;
-    std::vector<GroupNode> h_gnode;
-    // dry-mode taintTracker mirror (§8f rank 4): (node << 32 | group), sorted, unique
-    std::vector<uint64_t> h_trk;
-    int64_t trk_cap = 0;                                      // device capacity of trk_node/_group
-    // scale-down reaping (§8f rank 2): pods bound to nodes, per-node taint times
-    bool placed = false;                                      // pod binding current
-    bool node_removal = false;                                // taint times / no-delete loaded
-    PodRef* d_refs = nullptr;
-    uint32_t* d_e_pair = nullptr;
-    uint32_t *d_nrun_off = nullptr, *d_nrun_len = nullptr, *d_occ = nullptr, *d_rm_off = nullptr,
-             *d_rm_list = nullptr;                             // d_occ: [2][n_entries] (pair, default)
-    // host mirror of the placement: runs per node (capacity offsets, lengths), the pod at
-    // each run position, each pod's node and run position (pod events keep them current)
-    std::vector<uint32_t> h_run_off, h_run_len, h_pod_node;
-    std::vector<int32_t> h_run_pod;
-    std::vector<int64_t> h_pod_rpos;
-    int64_t *d_taint_s = nullptr, *d_soft = nullptr, *d_hard = nullptr;
-    uint8_t* d_no_delete = nullptr;
-    RmRec* d_rm_out = nullptr;
-    std::vector<uint32_t> h_rm_off;                           // [G + 1]
-    RmRec* h_rm = nullptr;                                    // K7 results (pinned copy)
-    uint8_t* h_istage = nullptr;                              // age-index build uploads (pinned)
-    size_t istage_cap = 0;
-    int64_t* h_words = nullptr;                               // esc_results' pod + node words (pinned)
-    size_t words_cap = 0;
-    // Small contexts (G <= HTOT_MAX_GROUPS): K4 writes every decided group's totals record
-    // straight to pinned host memory with its decision (<= 104 KB over PCIe), so esc_results
-    // copies nothing; tot_dec = the last enqueued step decided (the records are current).
-    esc_group_totals* h_tot = nullptr;
-    esc_group_totals* h_tot_dev = nullptr;
-    bool tot_dec = false;
-    std::vector<int64_t> h_soft, h_hard;                      // grace periods last uploaded
-    bool rm_valid = false;                                    // esc_try_remove results current
-    int64_t rm_nodes = -1;                                    // node count the reaping buffers are sized for
-    // newly registered nodes (calculateNewNodeMetrics, controller.go:157-189): the per-node
-    // instantiation time belongs to the node table (esc_load_nodes: every slot unknown)
-    int64_t *d_inst = nullptr, *d_nn_since = nullptr;         // [n_cap], [G]
-    uint32_t *d_nn_off = nullptr, *d_nn_list = nullptr;       // list offsets per group (as h_rm_off), the lists
-    esc_new_nodes* d_nn_out = nullptr;                        // [G]
-    std::vector<uint32_t> h_nn_off;                           // [G + 1]
-    std::vector<int64_t> h_nn_new;                            // [G] n_new of the last eval (list lengths)
-    bool nn_valid = false;                                    // esc_new_nodes_eval results current
-};
-
 namespace esc {
 const GroupIndex* ctx_group_index(const esc_ctx* ctx) { return &ctx->gi; }
 esc_multi_state* ctx_multi(const esc_ctx* c) { return c->multi; }
 void ctx_set_multi(esc_ctx* c, esc_multi_state* m) { c->multi = m; }
 hipStream_t ctx_stream(const esc_ctx* c) { return c->stream; }
 int ctx_device(const esc_ctx* c) { return c->device; }
-}
-
-namespace {
-
-// A kb_write_pod / kb_write_free put into the host copy of the K blocks.
-void put_kb(uint32_t* kb, int width, int64_t at, uint64_t v) {
-    if (width == 8) reinterpret_cast<int64_t*>(kb)[at] = (int64_t)v;
-    else if (width == 4) kb[at] = (uint32_t)v;
-    else reinterpret_cast<uint16_t*>(kb)[at] = (uint16_t)v;
-}
-
-// Host threads for the load-time layout passes: ESC_HOST_THREADS, else OMP_NUM_THREADS (the
-// GPU box sets 16, its CPU share per GPU), else min(16, hardware threads).
-int host_threads() {
-    int n = 0;
-    for (const char* e : {"ESC_HOST_THREADS", "OMP_NUM_THREADS"})
-        if (const char* v = std::getenv(e)) { n = std::atoi(v); if (n > 0) break; }
-    if (n <= 0) n = std::min<int>(16, std::max(1u, std::thread::hardware_concurrency()));
-    return std::max(1, std::min(n, 64));
-}
-
-// f(t, lo, hi) over T contiguous chunks of [0, n), one host thread each (in order for T = 1)
-template <class F>
-void par_chunks(int64_t n, int T, F&& f) {
-    if (T <= 1 || n < 4096) {
-        f(0, (int64_t)0, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    th.reserve(T);
-    for (int t = 0; t < T; ++t) th.emplace_back([&, t] { f(t, n * t / T, n * (t + 1) / T); });
-    for (auto& x : th) x.join();
-}
-
-// Spare C slots (esc_load_pods with esc_set_spare): room per slot, slots per 64-pod tile.
-constexpr int CS_SLOTS = 16, CS_XREG = 4, CS_XINIT = 2, CS_REC = CS_XREG + CS_XINIT + 1, CS_XP = 6;
-static_assert(CS_SLOTS * CS_REC <= 128 && CS_SLOTS * CS_XP <= 128, "a spare C tile stays on K1's C path");
-constexpr uint32_t CS_FLAGS = ESC_PF_DAEMONSET | ESC_PF_HAS_OVH | (uint32_t)CS_XREG << ESC_PF_XREG_SHIFT |
-                              (uint32_t)CS_XINIT << ESC_PF_XINIT_SHIFT | (uint32_t)CS_XP << ESC_PF_XPAIR_SHIFT;
-
-// K class of a pod (DESIGN.md §3): its record signature (at most 3 extra container
-// records and 3 extra pairs; -1: the C section) | packed << 7: 1 when its values fit the
-// packed block (kp_fits), 2 when they also fit the packed small block (kp8_fits, in a context
-// with fewer than KP8_PAIR_NONE group pairs).  xc_cpu / xc_mem: the pod's own records (null
-// when it has none).
-int pod_class_id(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
-                 const int64_t* xc_mem, uint32_t n_gp) {
-    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, np = pf_xpair(f);
-    if (xr + xi + ov > 3 || np > 3) return -1;
-    const int sig = (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
-    if (!kp_fits(f, cpu0, mem0, pair0, xc_cpu, xc_mem)) return sig;
-    return sig | (n_gp < KP8_PAIR_NONE && kp8_fits(cpu0, mem0) ? 2 : 1) * POD_SIG_IDS;
-}
-
-// A node's allocatable cpu fits K2's packed entry (NodeDev::e_pk).
-bool entry_cpu_packs(int64_t cpu) { return cpu >= 0 && cpu <= (int64_t)0xFFFFFFFF; }
-
-// K1 partial row stride: the pod slots (one per group pair + the default filter's)
-// rounded up to whole K3 columns.
-int64_t slot_stride(const esc_ctx* c) { return ((int64_t)c->gi.n_gp + 1 + FC_COL - 1) / FC_COL * FC_COL; }
-
-// The exchange buffer (SUM across ranks, reduce-scattered to the owners): the pods' words
-// in owner-major rows, [world][own_cap][PW_K] (DESIGN.md §7).
-int64_t xw_count(const esc_ctx* c) { return (int64_t)c->world * c->own_cap * PW_K; }
-int64_t* own_xwords(const esc_ctx* c) { return c->d_pwords + (int64_t)c->rank * c->own_cap * PW_K; }
-GroupList own_list(const esc_ctx* c) {
-    return GroupList{c->own_seq ? nullptr : c->d_own, (int32_t)c->h_own.size(), c->own_first};
-}
 
 GroupDev group_dev(const esc_ctx* c) {
     GroupDev g;
@@ -537,6 +132,135 @@ NodeDev node_dev(const esc_ctx* c) {
     return n;
 }
 
+void drop_graphs(esc_ctx* c) {
+    for (auto& g : c->graphs)
+        if (g) hipGraphExecDestroy(g);
+    c->graphs.clear();
+    for (auto& g : c->rgraphs)
+        if (g) hipGraphExecDestroy(g);
+    c->rgraphs.clear();
+}
+
+// A planned layout (esc_node_layout.h) becomes the context's, once its device tables are in
+// place (esc_load_nodes, esc_nodes_rebuild).  Nothing here fails.
+void commit_layout(esc_ctx* c, NodeLayout& L, bool pk_ok) {
+    c->pair_lo.swap(L.pair_lo); c->pair_next.swap(L.pair_next); c->pair_end.swap(L.pair_end);
+    c->n_entries = L.n_entries; c->n_pieces = L.n_pieces; c->n_spans = (int64_t)L.span_off.size() - 1;
+    c->pc_lo = L.pc_lo; c->pc_hi = L.pc_hi;
+    c->node_bytes = L.node_bytes;
+    c->e_pk_ok = pk_ok;
+    c->h_nn_off.swap(L.list_off);
+    c->h_gn.clear();
+}
+
+RemovalDev removal_dev(const esc_ctx* c, int64_t now_ns) {
+    RemovalDev r;
+    r.e_pair = c->d_e_pair; r.n_entries = c->n_entries;
+    r.taint_s = c->d_taint_s; r.no_delete = c->d_no_delete;
+    r.nrun_off = c->d_nrun_off; r.nrun_len = c->d_nrun_len; r.refs = c->d_refs;
+    r.xp = c->pods[c->cur].xp;
+    r.occ_pair = c->d_occ; r.occ_def = c->d_occ + std::max<int64_t>(c->n_entries, 0);
+    r.soft_ns = c->d_soft; r.hard_ns = c->d_hard;
+    r.rm_off = c->d_rm_off; r.rm_list = c->d_rm_list; r.out = c->d_rm_out; r.now_ns = now_ns;
+    return r;
+}
+
+// The maintained occupancy words (see esc_ctx::d_occ_local) as K6 / the deltas address them.
+RemovalDev occ_dev(const esc_ctx* c) {
+    RemovalDev r = removal_dev(c, 0);
+    uint32_t* o = c->d_occ_local ? c->d_occ_local : c->d_occ;
+    r.occ_pair = o;
+    r.occ_def = o + std::max<int64_t>(c->n_entries, 0);
+    return r;
+}
+
+// Device copy of the node -> entries map (node slots up to n_cap, entries up to n_entries).
+int32_t ensure_ne_dev(esc_ctx* c) {
+    const int64_t nn = (int64_t)c->ne_off.size() - 1, np = (int64_t)c->ne_pos.size();
+    if (nn == c->ne_dev_nodes && np == c->ne_dev_pos) return ESC_OK;
+    if (!c->d_ne_off) {
+        HIP_TRY(dalloc(&c->d_ne_off, (size_t)std::max<int64_t>(c->n_cap, nn) + 1));
+        HIP_TRY(dalloc(&c->d_ne_pos, (size_t)std::max<int64_t>(c->n_entries, std::max<int64_t>(np, 1))));
+    }
+    std::vector<uint32_t> off(c->ne_off);
+    off.resize((size_t)std::max<int64_t>(c->n_cap, nn) + 1, c->ne_off.back());   // free slots: no entries
+    HIP_TRY(hipMemcpy(c->d_ne_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (np) HIP_TRY(hipMemcpy(c->d_ne_pos, c->ne_pos.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    c->ne_dev_nodes = nn;
+    c->ne_dev_pos = np;
+    return ESC_OK;
+}
+
+// K6 over every live entry into the maintained words (esc_load_placement).
+int32_t occ_recount(esc_ctx* c) {
+    if (int32_t rc = ensure_ne_dev(c)) return rc;
+    HIP_TRY(launch_occupancy(node_dev(c), group_dev(c), occ_dev(c), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ESC_OK;
+}
+
+}  // namespace esc
+
+namespace {
+
+// A kb_write_pod / kb_write_free put into the host copy of the K blocks.
+void put_kb(uint32_t* kb, int width, int64_t at, uint64_t v) {
+    if (width == 8) reinterpret_cast<int64_t*>(kb)[at] = (int64_t)v;
+    else if (width == 4) kb[at] = (uint32_t)v;
+    else reinterpret_cast<uint16_t*>(kb)[at] = (uint16_t)v;
+}
+
+// Host threads for the load-time layout passes: ESC_HOST_THREADS, else OMP_NUM_THREADS (the
+// GPU box sets 16, its CPU share per GPU), else min(16, hardware threads).
+int host_threads() {
+    int n = 0;
+    for (const char* e : {"ESC_HOST_THREADS", "OMP_NUM_THREADS"})
+        if (const char* v = std::getenv(e)) { n = std::atoi(v); if (n > 0) break; }
+    if (n <= 0) n = std::min<int>(16, std::max(1u, std::thread::hardware_concurrency()));
+    return std::max(1, std::min(n, 64));
+}
+
+// f(t, lo, hi) over T contiguous chunks of [0, n), one host thread each (in order for T = 1)
+template <class F>
+void par_chunks(int64_t n, int T, F&& f) {
+    if (T <= 1 || n < 4096) {
+        f(0, (int64_t)0, n);
+        return;
+    }
+    std::vector<std::thread> th;
+    th.reserve(T);
+    for (int t = 0; t < T; ++t) th.emplace_back([&, t] { f(t, n * t / T, n * (t + 1) / T); });
+    for (auto& x : th) x.join();
+}
+
+// Spare C slots (esc_load_pods with esc_set_spare): room per slot, slots per 64-pod tile.
+constexpr int CS_SLOTS = 16, CS_XREG = 4, CS_XINIT = 2, CS_REC = CS_XREG + CS_XINIT + 1, CS_XP = 6;
+static_assert(CS_SLOTS * CS_REC <= 128 && CS_SLOTS * CS_XP <= 128, "a spare C tile stays on K1's C path");
+constexpr uint32_t CS_FLAGS = ESC_PF_DAEMONSET | ESC_PF_HAS_OVH | (uint32_t)CS_XREG << ESC_PF_XREG_SHIFT |
+                              (uint32_t)CS_XINIT << ESC_PF_XINIT_SHIFT | (uint32_t)CS_XP << ESC_PF_XPAIR_SHIFT;
+
+// K class of a pod (DESIGN.md §3): its record signature (at most 3 extra container
+// records and 3 extra pairs; -1: the C section) | packed << 7: 1 when its values fit the
+// packed block (kp_fits), 2 when they also fit the packed small block (kp8_fits, in a context
+// with fewer than KP8_PAIR_NONE group pairs).  xc_cpu / xc_mem: the pod's own records (null
+// when it has none).
+int pod_class_id(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
+                 const int64_t* xc_mem, uint32_t n_gp) {
+    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, np = pf_xpair(f);
+    if (xr + xi + ov > 3 || np > 3) return -1;
+    const int sig = (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
+    if (!kp_fits(f, cpu0, mem0, pair0, xc_cpu, xc_mem)) return sig;
+    return sig | (n_gp < KP8_PAIR_NONE && kp8_fits(cpu0, mem0) ? 2 : 1) * POD_SIG_IDS;
+}
+
+// The exchange buffer (SUM across ranks, reduce-scattered to the owners): the pods' words
+// in owner-major rows, [world][own_cap][PW_K] (DESIGN.md §7).
+int64_t xw_count(const esc_ctx* c) { return (int64_t)c->world * c->own_cap * PW_K; }
+int64_t* own_xwords(const esc_ctx* c) { return c->d_pwords + (int64_t)c->rank * c->own_cap * PW_K; }
+GroupList own_list(const esc_ctx* c) {
+    return GroupList{c->own_seq ? nullptr : c->d_own, (int32_t)c->h_own.size(), c->own_first};
+}
+
 void params_from(GroupParams& p, const esc_group_spec& s, const esc_group_state* st) {
     p.min_nodes = s.min_nodes; p.max_nodes = s.max_nodes;
     p.taint_upper = s.taint_upper_pct; p.taint_lower = s.taint_lower_pct; p.scale_up = s.scale_up_pct;
@@ -547,17 +271,6 @@ void params_from(GroupParams& p, const esc_group_spec& s, const esc_group_state*
     p.cached_cpu = st ? st->cached_cpu_m : 0;
     p.cached_mem = st ? st->cached_mem_b : 0;
 }
-
-void drop_graphs(esc_ctx* c) {
-    for (auto& g : c->graphs)
-        if (g) hipGraphExecDestroy(g);
-    c->graphs.clear();
-    for (auto& g : c->rgraphs)
-        if (g) hipGraphExecDestroy(g);
-    c->rgraphs.clear();
-}
-
-int32_t enqueue_step(esc_ctx* c, int r, bool decide, bool copy_out);
 
 // The look-back bound of the next K5 launch (ordering or listing): LOOKBACK_SPINS, except
 // for launches a measurement-library test set to give up at once (esc_debug_lookback_fail,
@@ -613,37 +326,6 @@ hipError_t enqueue_order(esc_ctx* c, hipStream_t st) {
                                c->d_ord, c->d_seg, st);
 }
 
-// Replays (capturing on first use) the per-replica graph of enqueue_step(r, decide, decide)
-// on the context's stream: one launch instead of the step's kernels, events and waits.
-// With the ordering in the step there is one graph per (replica, ordering parity): the
-// split ordering alternates two status arrays (k_ord_split), and a graph holds its launch's.
-int32_t replay_step(esc_ctx* c, std::vector<hipGraphExec_t>& gs, int r, bool decide) {
-    const int nrep = (int)c->pods.size();
-    if ((int)gs.size() != 2 * nrep) {
-        for (auto& g : gs)
-            if (g) hipGraphExecDestroy(g);
-        gs.assign(2 * (size_t)nrep, nullptr);
-    }
-    const bool ord = c->order_in_step;
-    const int k = 2 * r + (ord ? c->ord_parity : 0);
-    if (!gs[k]) {
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        const int32_t rc = enqueue_step(c, r, decide, decide);          // flips the parity (ord)
-        hipError_t e = hipStreamEndCapture(c->stream, &graph);
-        if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) return fail_hip(e, "hipStreamEndCapture");
-        e = hipGraphInstantiate(&gs[k], graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (e != hipSuccess) return fail_hip(e, "hipGraphInstantiate");
-    } else if (ord) {
-        c->ord_parity ^= 1;
-        c->ord_failed = false;
-    }
-    HIP_TRY(hipGraphLaunch(gs[k], c->stream));
-    return ESC_OK;
-}
-
 void release_work(esc_ctx* c) {
     dfree(c->d_k1seg); dfree(c->d_pod_part); dfree(c->d_wide_pod); dfree(c->d_trk_acc);
     dfree(c->d_k1_trace);
@@ -683,6 +365,10 @@ void release_new_nodes(esc_ctx* c) {
     c->h_nn_new.clear();
     c->nn_valid = false;
 }
+
+}  // namespace
+
+namespace esc {
 
 void release_sort(esc_ctx* c) {
     drop_graphs(c);                                     // captured steps hold the index's buffers
@@ -974,6 +660,10 @@ int32_t build_age_index(esc_ctx* c) {
     return ESC_OK;
 }
 
+}  // namespace esc
+
+namespace {
+
 // K1 work plan: every workgroup's K tiles as at most K1_SEGS runs of one
 // class, balanced in work weight (16-B loads), with at most two class boundaries per
 // workgroup.  A class run restarts the workgroup's load pipeline (its first tiles' full
@@ -1111,18 +801,6 @@ std::vector<int64_t> pair_counts(const esc_ctx* c, const esc_node_soa* s) {
     return cnt;
 }
 
-// A planned layout (esc_node_layout.h) becomes the context's, once its device tables are in
-// place (esc_load_nodes, esc_nodes_rebuild).  Nothing here fails.
-void commit_layout(esc_ctx* c, NodeLayout& L, bool pk_ok) {
-    c->pair_lo.swap(L.pair_lo); c->pair_next.swap(L.pair_next); c->pair_end.swap(L.pair_end);
-    c->n_entries = L.n_entries; c->n_pieces = L.n_pieces; c->n_spans = (int64_t)L.span_off.size() - 1;
-    c->pc_lo = L.pc_lo; c->pc_hi = L.pc_hi;
-    c->node_bytes = L.node_bytes;
-    c->e_pk_ok = pk_ok;
-    c->h_nn_off.swap(L.list_off);
-    c->h_gn.clear();
-}
-
 // Pod accumulator slots: one per group pair + one for the default filter.
 int64_t pod_slots(const esc_ctx* c) { return (int64_t)c->gi.n_gp + 1; }
 
@@ -1179,14 +857,9 @@ int32_t touch_refresh(esc_ctx* c, const std::vector<int64_t>& plan) {
     return ESC_OK;
 }
 
-// Marks the columns a pod written into K slot q of class ci adds to (esc_pods_upsert);
-// true when its workgroup did not touch one of them yet (the lists need an upload).
-bool touch_mark(esc_ctx* c, int32_t ci, int64_t q, uint32_t f, uint32_t pair0, const uint32_t* xp) {
-    if (!c->touch_on || (f & ESC_PF_DAEMONSET)) return false;
-    const int64_t t = c->h_cls[ci].t0 + q / TILE;
-    auto it = std::upper_bound(c->h_tile_wg.begin(), c->h_tile_wg.end(), std::array<int64_t, 3>{t, INT64_MAX, INT64_MAX});
-    if (it == c->h_tile_wg.begin() || t >= (it - 1)->at(1)) return false;   // a tile no workgroup streams (none)
-    uint32_t* row = c->h_touch.data() + (size_t)(it - 1)->at(2) * c->touch_tw;
+// Marks in a workgroup's touch-bitmap row the columns of a pod's group pairs; true when one
+// of them was not marked yet (the lists need an upload).
+bool touch_mark_row(const esc_ctx* c, uint32_t* row, uint32_t f, uint32_t pair0, const uint32_t* xp) {
     bool grew = false;
     auto mark = [&](uint32_t slot) {
         const uint32_t col = slot / FC_COL, bit = 1u << (col & 31);
@@ -1199,22 +872,22 @@ bool touch_mark(esc_ctx* c, int32_t ci, int64_t q, uint32_t f, uint32_t pair0, c
     return grew;
 }
 
+// Marks the columns a pod written into K slot q of class ci adds to (esc_pods_upsert);
+// true when its workgroup did not touch one of them yet.
+bool touch_mark(esc_ctx* c, int32_t ci, int64_t q, uint32_t f, uint32_t pair0, const uint32_t* xp) {
+    if (!c->touch_on || (f & ESC_PF_DAEMONSET)) return false;
+    const int64_t t = c->h_cls[ci].t0 + q / TILE;
+    auto it = std::upper_bound(c->h_tile_wg.begin(), c->h_tile_wg.end(), std::array<int64_t, 3>{t, INT64_MAX, INT64_MAX});
+    if (it == c->h_tile_wg.begin() || t >= (it - 1)->at(1)) return false;   // a tile no workgroup streams (none)
+    return touch_mark_row(c, c->h_touch.data() + (size_t)(it - 1)->at(2) * c->touch_tw, f, pair0, xp);
+}
+
 // The same for a pod written into C slot d (K1 and k_touch give workgroup b the C tiles
 // [b * per, (b + 1) * per), per = ceil(c_tiles / nblk)).
 bool touch_mark_c(esc_ctx* c, int64_t d, uint32_t f, uint32_t pair0, const uint32_t* xp) {
     if (!c->touch_on || (f & ESC_PF_DAEMONSET) || c->nblk <= 0) return false;
     const int64_t per = (c->c_tiles + c->nblk - 1) / c->nblk, b = (d / CTILE) / std::max<int64_t>(per, 1);
-    uint32_t* row = c->h_touch.data() + (size_t)b * c->touch_tw;
-    bool grew = false;
-    auto mark = [&](uint32_t slot) {
-        const uint32_t col = slot / FC_COL, bit = 1u << (col & 31);
-        if (!(row[col >> 5] & bit)) { row[col >> 5] |= bit; grew = true; }
-    };
-    const uint32_t n_gp = c->gi.n_gp;
-    if (pair0 < n_gp) mark(pair0);
-    for (uint32_t k = 0; k < pf_xpair(f); ++k)
-        if (xp[k] < n_gp) mark(xp[k]);
-    return grew;
+    return touch_mark_row(c, c->h_touch.data() + (size_t)b * c->touch_tw, f, pair0, xp);
 }
 
 // The rank owning group g's node side: the one whose pair range holds the group's pair
@@ -1224,8 +897,6 @@ int32_t group_owner_rank(const esc_ctx* c, int32_t g) {
     const uint32_t q = c->gi.gpair[(size_t)g];
     return (int32_t)(std::upper_bound(c->q_bounds.begin(), c->q_bounds.end() - 1, q) - c->q_bounds.begin()) - 1;
 }
-
-constexpr uint32_t STALE_PODS = 1, STALE_NODES = 2;
 
 // The apply phase of an event batch (its checks passed): on failure the context is marked
 // stale (esc_ctx::stale) until the matching reload.
@@ -1451,6 +1122,37 @@ int32_t check_ready(esc_ctx* c, bool fit = true) {
     // caller binds one of the new size
     if (fit && c->bound_pwords && xw_count(c) > c->bound_words) return ESC_E_STATE;
     if (c->order_in_step && !c->age_ok) return ESC_E_STATE;   // the age index build failed: rebuild
+    return ESC_OK;
+}
+
+// Replays (capturing on first use) the per-replica graph of enqueue_step(r, decide, decide)
+// on the context's stream: one launch instead of the step's kernels, events and waits.
+// With the ordering in the step there is one graph per (replica, ordering parity): the
+// split ordering alternates two status arrays (k_ord_split), and a graph holds its launch's.
+int32_t replay_step(esc_ctx* c, std::vector<hipGraphExec_t>& gs, int r, bool decide) {
+    const int nrep = (int)c->pods.size();
+    if ((int)gs.size() != 2 * nrep) {
+        for (auto& g : gs)
+            if (g) hipGraphExecDestroy(g);
+        gs.assign(2 * (size_t)nrep, nullptr);
+    }
+    const bool ord = c->order_in_step;
+    const int k = 2 * r + (ord ? c->ord_parity : 0);
+    if (!gs[k]) {
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        const int32_t rc = enqueue_step(c, r, decide, decide);          // flips the parity (ord)
+        hipError_t e = hipStreamEndCapture(c->stream, &graph);
+        if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+        if (e != hipSuccess) return fail_hip(e, "hipStreamEndCapture");
+        e = hipGraphInstantiate(&gs[k], graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (e != hipSuccess) return fail_hip(e, "hipGraphInstantiate");
+    } else if (ord) {
+        c->ord_parity ^= 1;
+        c->ord_failed = false;
+    }
+    HIP_TRY(hipGraphLaunch(gs[k], c->stream));
     return ESC_OK;
 }
 
@@ -2994,42 +2696,6 @@ int64_t pod_slot(const esc_ctx* c, int64_t id) {
     return ci >= 0 ? (c->h_cls[ci].t0 + d / TILE) * TILE + d % TILE : d;
 }
 
-RemovalDev removal_dev(const esc_ctx* c, int64_t now_ns);
-
-// The maintained occupancy words (see esc_ctx::d_occ_local) as K6 / the deltas address them.
-RemovalDev occ_dev(const esc_ctx* c) {
-    RemovalDev r = removal_dev(c, 0);
-    uint32_t* o = c->d_occ_local ? c->d_occ_local : c->d_occ;
-    r.occ_pair = o;
-    r.occ_def = o + std::max<int64_t>(c->n_entries, 0);
-    return r;
-}
-
-// Device copy of the node -> entries map (node slots up to n_cap, entries up to n_entries).
-int32_t ensure_ne_dev(esc_ctx* c) {
-    const int64_t nn = (int64_t)c->ne_off.size() - 1, np = (int64_t)c->ne_pos.size();
-    if (nn == c->ne_dev_nodes && np == c->ne_dev_pos) return ESC_OK;
-    if (!c->d_ne_off) {
-        HIP_TRY(dalloc(&c->d_ne_off, (size_t)std::max<int64_t>(c->n_cap, nn) + 1));
-        HIP_TRY(dalloc(&c->d_ne_pos, (size_t)std::max<int64_t>(c->n_entries, std::max<int64_t>(np, 1))));
-    }
-    std::vector<uint32_t> off(c->ne_off);
-    off.resize((size_t)std::max<int64_t>(c->n_cap, nn) + 1, c->ne_off.back());   // free slots: no entries
-    HIP_TRY(hipMemcpy(c->d_ne_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    if (np) HIP_TRY(hipMemcpy(c->d_ne_pos, c->ne_pos.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-    c->ne_dev_nodes = nn;
-    c->ne_dev_pos = np;
-    return ESC_OK;
-}
-
-// K6 over every live entry into the maintained words (esc_load_placement).
-int32_t occ_recount(esc_ctx* c) {
-    if (int32_t rc = ensure_ne_dev(c)) return rc;
-    HIP_TRY(launch_occupancy(node_dev(c), group_dev(c), occ_dev(c), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return ESC_OK;
-}
-
 // The PodRefs now at run positions pos (on nodes node) added to (+1) or removed from (-1)
 // the maintained occupancy words: called before the runs change for the pods an event
 // moves or drops, and after for the pods it binds or rewrites.
@@ -3061,18 +2727,6 @@ void bound_of(const esc_ctx* c, const int64_t* ids, int64_t n, std::vector<uint3
             node.push_back(c->h_pod_node[id]);
         }
     }
-}
-
-RemovalDev removal_dev(const esc_ctx* c, int64_t now_ns) {
-    RemovalDev r;
-    r.e_pair = c->d_e_pair; r.n_entries = c->n_entries;
-    r.taint_s = c->d_taint_s; r.no_delete = c->d_no_delete;
-    r.nrun_off = c->d_nrun_off; r.nrun_len = c->d_nrun_len; r.refs = c->d_refs;
-    r.xp = c->pods[c->cur].xp;
-    r.occ_pair = c->d_occ; r.occ_def = c->d_occ + std::max<int64_t>(c->n_entries, 0);
-    r.soft_ns = c->d_soft; r.hard_ns = c->d_hard;
-    r.rm_off = c->d_rm_off; r.rm_list = c->d_rm_list; r.out = c->d_rm_out; r.now_ns = now_ns;
-    return r;
 }
 
 // Placement upkeep under pod events (§8f rank 2): a bound pod's PodRef lives in its node's
@@ -3187,12 +2841,6 @@ uint32_t memb_flags(const esc_ctx* c, int64_t j, uint32_t mb) {
 }
 
 int64_t created_of(const esc_ctx* c, uint32_t j) { return c->h_created[(int64_t)j - c->node_lo]; }
-
-// Does this rank own group g's node side (its pair in [q_lo, q_hi))?
-bool owns_group(const esc_ctx* c, uint32_t g) {
-    const uint32_t q = c->gi.gpair[g];
-    return q >= c->q_lo && q < c->q_hi;
-}
 
 // Host mirror of the regions' node ids (fetched once, then kept in step with every patch).
 int32_t ensure_gn(esc_ctx* c) {
@@ -3450,8 +3098,6 @@ bool c_room(uint32_t cf, uint32_t f) {
     return pf_xreg(f) <= pf_xreg(cf) && pf_xinit(f) <= pf_xinit(cf) && (!(f & ESC_PF_HAS_OVH) || (cf & ESC_PF_HAS_OVH)) &&
            pf_xpair(f) <= pf_xpair(cf);
 }
-
-bool touch_mark_c(esc_ctx* c, int64_t d, uint32_t f, uint32_t pair0, const uint32_t* xp);
 
 // Writes pod i of the batch into C slot d (its room: the slot's flags' counts; the pod's
 // records and pairs first of each kind, the rest neutral — 0 for added records, absent keys
@@ -4011,14 +3657,6 @@ void group_pairs(uint32_t n_gp, uint32_t label0, uint32_t nx, const uint32_t* xl
     if (label0 < n_gp) out.push_back(label0);
     for (uint32_t k = 0; k < nx; ++k)
         if (xl[k] < n_gp) out.push_back(xl[k]);
-}
-
-// the group pair of pair-major entry e (NONE: a pair no group uses)
-uint32_t entry_pair(const esc_ctx* c, uint32_t e) {
-    const uint32_t n_gp = c->gi.n_gp;
-    if (!n_gp || e >= c->pair_end[n_gp - 1]) return NONE;
-    const uint32_t q = (uint32_t)(std::upper_bound(c->pair_lo.begin(), c->pair_lo.end(), e) - c->pair_lo.begin()) - 1;
-    return e < c->pair_end[q] ? q : NONE;
 }
 
 // Node j's own retired entry of pair q (an entry it left earlier and nobody took since),
@@ -4722,555 +4360,6 @@ int32_t esc_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known, 
     }
     return ESC_OK;
 }
-
-}  // extern "C"
-
-// ------------------------------------------------ node-side rebuild
-namespace {
-
-// The buffers a rebuild builds beside the resident ones.  The swap exchanges them with the
-// context's, so whatever this holds when it goes out of scope — the new buffers of a rebuild
-// that failed, the old ones of one that succeeded, the scratch of both — is released.
-struct RebuildBufs {
-    NodeDerived nb;                               // entries, pieces, spans, rows, gnode, xl, xl_off, trk_start
-    uint32_t *ne_off = nullptr, *ne_pos = nullptr, *e_pair = nullptr, *occ = nullptr, *occ_local = nullptr;
-    uint32_t *nn_off = nullptr, *nn_list = nullptr, *rm_off = nullptr, *rm_list = nullptr;
-    uint8_t* blob = nullptr;                      // the staged layout tables
-    uint64_t* elems[2] = {nullptr, nullptr};
-    uint32_t *hist = nullptr, *tot = nullptr;
-    ~RebuildBufs() {
-        nb.release();
-        dfree(ne_off); dfree(ne_pos); dfree(e_pair); dfree(occ); dfree(occ_local);
-        dfree(nn_off); dfree(nn_list); dfree(rm_off); dfree(rm_list);
-        dfree(blob); dfree(elems[0]); dfree(elems[1]); dfree(hist); dfree(tot);
-    }
-};
-
-// Seconds since the first call (the probe's split of a rebuild, esc_debug_rebuild_times).
-double rebuild_clock() {
-    timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-}
-thread_local double g_rebuild_ms[6];              // host layout, upload, kernels, mirrors, occupancy, age index
-
-int32_t nodes_rebuild_one(esc_ctx* c) {
-    const uint32_t n_gp = c->gi.n_gp;
-    const int32_t G = c->gi.G;
-    const int64_t N = c->n_nodes, NC = c->n_cap;
-    const double sf = c->spare_frac;
-    if ((int64_t)c->h_nflags.size() < NC || (int64_t)c->pair_live.size() != (int64_t)n_gp) return ESC_E_STATE;
-    hipSetDevice(c->device);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    double t0 = rebuild_clock();
-    for (double& x : g_rebuild_ms) x = 0;
-    // ---- the layout, from the host's counts alone
-    // the tracker index and bit first: the entries carry the bit
-    std::vector<uint32_t> trk_start((size_t)std::max<int64_t>(NC, 1), NONE);
-    for (int64_t k = (int64_t)c->h_trk.size() - 1; k >= 0; --k) {
-        const uint64_t j = c->h_trk[k] >> 32;
-        if ((int64_t)j >= N) return fail_hip(hipErrorUnknown, "nodes rebuild: tracker mirror");
-        trk_start[j] = (uint32_t)k;
-    }
-    std::vector<uint32_t> nflags(c->h_nflags.begin(), c->h_nflags.begin() + NC);
-    std::vector<uint32_t> ne_off((size_t)NC + 1, 0), xl_off((size_t)std::max<int64_t>(NC, 1), 0);
-    uint64_t m = 0, xw = 0;
-    uint32_t max_pair = 0;
-    bool pk_ok = true;
-    for (int64_t i = 0; i < NC; ++i) {
-        ne_off[i] = (uint32_t)m;
-        xl_off[i] = (uint32_t)xw;
-        uint32_t& f = nflags[i];
-        if (i >= N || (f & ESC_NF_ABSENT)) continue;
-        f = (f & ~ESC_NF_TRACKED) | (trk_start[i] != NONE ? ESC_NF_TRACKED : 0u);
-        pk_ok = pk_ok && entry_cpu_packs(c->h_ncpu[i]);
-        if (c->h_label0[i] == NONE) continue;
-        const uint32_t nx = nf_xlbl(f);
-        if ((uint64_t)c->h_xl_off[i] + nx > c->h_xl.size()) return fail_hip(hipErrorUnknown, "nodes rebuild: label mirror");
-        max_pair = std::max(max_pair, nx ? c->h_xl[c->h_xl_off[i] + nx - 1] : c->h_label0[i]);
-        m += 1 + nx;
-        xw += nx;
-        if (m >= 0xFFFFFFFFull) return ESC_E_LIMIT;
-    }
-    ne_off[NC] = (uint32_t)m;
-    const int64_t M = (int64_t)m;
-    // the extra labels, compacted to the live nodes' words
-    std::vector<uint32_t> h_xl((size_t)xw);
-    for (int64_t i = 0; i < N; ++i) {
-        if ((nflags[i] & ESC_NF_ABSENT) || c->h_label0[i] == NONE) continue;
-        const uint32_t nx = nf_xlbl(nflags[i]);
-        std::copy_n(c->h_xl.begin() + c->h_xl_off[i], nx, h_xl.begin() + xl_off[i]);
-    }
-    const int64_t xl_cap = label_words((int64_t)xw, sf);
-    // group pairs: live entries sorted by node (start: where a pair's begin among the sorted
-    // elements), then their spare ones; the entries of pairs no group selects follow all of
-    // them as one run (pair NONE: nothing reads a piece of such a pair).  This rank's share
-    // stays inside the kept owner bounds.  The ranges, pieces, spans and list offsets are
-    // plan_node_layout's (esc_node_layout.h), as at a load.
-    std::vector<uint32_t> start((size_t)n_gp + 1);
-    uint64_t s_acc = 0;
-    for (uint32_t q = 0; q < n_gp; ++q) {
-        if (c->pair_live[q] < 0) return fail_hip(hipErrorUnknown, "nodes rebuild: pair mirror");
-        start[q] = (uint32_t)s_acc;
-        s_acc += (uint64_t)c->pair_live[q];
-    }
-    start[n_gp] = (uint32_t)s_acc;
-    if ((int64_t)s_acc > M) return fail_hip(hipErrorUnknown, "nodes rebuild: pair mirror");
-    NodeLayout L;
-    if (const int32_t rc = plan_node_layout(L, c->pair_live, sf, {TailRun{NONE, (uint64_t)M - s_acc}}, c->q_lo, c->q_hi,
-                                            pk_ok, c->gi.gpair.data(), G))
-        return rc;
-    const int64_t E = L.n_entries, n_pieces = L.n_pieces;
-    const uint64_t spare_total = (uint64_t)(E - M);
-    // ---- one staged copy of every table (the error word, zero, at its end)
-    struct Part { const std::vector<uint32_t>* v; size_t at; };
-    Part parts[] = {{&ne_off, 0}, {&xl_off, 0}, {&trk_start, 0}, {&start, 0}, {&L.pair_lo, 0}, {&L.piece_off, 0},
-                    {&L.piece_pair, 0}, {&L.pp_off, 0}, {&L.span_off, 0}, {&L.span_e, 0}, {&L.list_off, 0}};
-    enum { P_NE, P_XLO, P_TRK, P_START, P_LO, P_POFF, P_PPAIR, P_PP, P_SOFF, P_SE, P_LIST, P_N };
-    size_t bytes = 0;
-    for (Part& p : parts) { p.at = bytes; bytes += (p.v->size() * 4 + 255) & ~(size_t)255; }
-    const size_t err_at = bytes;
-    bytes += 256;
-    std::vector<uint8_t> stage(bytes, 0);
-    for (const Part& p : parts)
-        if (!p.v->empty()) std::memcpy(stage.data() + p.at, p.v->data(), p.v->size() * 4);
-    g_rebuild_ms[0] = (rebuild_clock() - t0) * 1e3;
-    t0 = rebuild_clock();
-    // ---- the new buffers, beside the resident ones
-    RebuildBufs B;
-    NodeDerived& b = B.nb;
-    const size_t Ez = (size_t)std::max<int64_t>(E, 1), Pz = (size_t)std::max<int64_t>(n_pieces, 1);
-    const bool reap = c->d_e_pair != nullptr;     // esc_load_placement's per-entry buffers exist
-    HIP_TRY(dalloc(&B.blob, bytes));
-    HIP_TRY(dalloc(&b.e_flags, Ez)); HIP_TRY(dalloc(&b.e_node, Ez)); HIP_TRY(dalloc(&b.e_cpu, Ez));
-    HIP_TRY(dalloc(&b.e_mem, Ez)); HIP_TRY(dalloc(&b.e_pk, Ez));
-    HIP_TRY(dalloc(&b.piece_off, L.piece_off.size())); HIP_TRY(dalloc(&b.piece_pair, Pz));
-    HIP_TRY(dalloc(&b.pp_off, L.pp_off.size())); HIP_TRY(dalloc(&b.span_off, L.span_off.size()));
-    HIP_TRY(dalloc(&b.span_e, L.span_e.size())); HIP_TRY(dalloc(&b.rows, Pz * NR_K));
-    HIP_TRY(dalloc(&b.gnode, (size_t)G));
-    HIP_TRY(dalloc(&b.xl, (size_t)xl_cap)); HIP_TRY(dalloc(&b.xl_off, xl_off.size()));
-    HIP_TRY(dalloc(&b.trk_start, trk_start.size()));
-    HIP_TRY(dalloc(&B.ne_off, ne_off.size())); HIP_TRY(dalloc(&B.ne_pos, Ez));
-    HIP_TRY(dalloc(&B.nn_off, (size_t)G)); HIP_TRY(dalloc(&B.nn_list, std::max<uint32_t>(L.list_off[G], 1)));
-    if (reap) {
-        HIP_TRY(dalloc(&B.e_pair, Ez)); HIP_TRY(dalloc(&B.occ, 2 * Ez));
-        if (c->d_occ_local) HIP_TRY(dalloc(&B.occ_local, 2 * Ez));
-        HIP_TRY(dalloc(&B.rm_off, (size_t)G)); HIP_TRY(dalloc(&B.rm_list, std::max<uint32_t>(L.list_off[G], 1)));
-    }
-    HIP_TRY(dalloc(&B.elems[0], (size_t)M)); HIP_TRY(dalloc(&B.elems[1], (size_t)M));
-    HIP_TRY(dalloc(&B.hist, std::max(sort_hist_words(std::max<int64_t>(M, 1)), sort_hist_words(1) * 4)));
-    HIP_TRY(dalloc(&B.tot, 256));
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemcpyAsync(B.blob, stage.data(), bytes, hipMemcpyHostToDevice, st));
-    auto view = [&](int k) { return reinterpret_cast<uint32_t*>(B.blob + parts[k].at); };
-    auto keep = [&](uint32_t* dst, int k, size_t words) -> hipError_t {   // a table the snapshot keeps: its own buffer
-        return words ? hipMemcpyAsync(dst, view(k), words * 4, hipMemcpyDeviceToDevice, st) : hipSuccess;
-    };
-    HIP_TRY(keep(B.ne_off, P_NE, ne_off.size())); HIP_TRY(keep(b.xl_off, P_XLO, xl_off.size()));
-    HIP_TRY(keep(b.trk_start, P_TRK, trk_start.size())); HIP_TRY(keep(b.piece_off, P_POFF, L.piece_off.size()));
-    HIP_TRY(keep(b.piece_pair, P_PPAIR, L.piece_pair.size())); HIP_TRY(keep(b.pp_off, P_PP, L.pp_off.size()));
-    HIP_TRY(keep(b.span_off, P_SOFF, L.span_off.size())); HIP_TRY(keep(b.span_e, P_SE, L.span_e.size()));
-    HIP_TRY(keep(B.nn_off, P_LIST, (size_t)G));
-    if (reap) HIP_TRY(keep(B.rm_off, P_LIST, (size_t)G));
-#if ESC_MEASURE
-    HIP_TRY(hipStreamSynchronize(st));                       // (the probe's split: the upload's end)
-    g_rebuild_ms[1] = (rebuild_clock() - t0) * 1e3;
-    t0 = rebuild_clock();
-#endif
-    // ---- list, sort, place
-    RebuildDev R{};
-    R.flags = c->nodes.flags; R.label0 = c->nodes.label0; R.xl_off = c->nodes.d.xl_off; R.xl = c->nodes.d.xl;
-    R.cpu = c->nodes.cpu; R.mem = c->nodes.mem;
-    R.n_cap = NC; R.xl_len = c->xl_used;
-    R.ne_off = view(P_NE); R.xl_off_new = view(P_XLO); R.trk_start = view(P_TRK); R.start = view(P_START);
-    R.pair_lo = view(P_LO); R.piece_off = view(P_POFF); R.piece_pair = view(P_PPAIR);
-    R.n_pieces = n_pieces; R.n_elems = M; R.n_entries = E; R.xl_new_cap = xl_cap;
-    R.n_gp = n_gp; R.spare_total = (uint32_t)spare_total;
-    R.xl_new = b.xl; R.e_flags = b.e_flags; R.e_node = b.e_node; R.e_pair = B.e_pair; R.e_cpu = b.e_cpu;
-    R.e_mem = b.e_mem; R.e_pk = b.e_pk; R.ne_pos = B.ne_pos;
-    R.err = reinterpret_cast<uint32_t*>(B.blob + err_at);
-    HIP_TRY(launch_nodes_rebuild(R, B.elems, B.hist, B.tot, bit_width(max_pair), st));
-    uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, R.err, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                       // the build's wait
-    if (err) {
-        std::snprintf(g_last_error, sizeof g_last_error, "nodes rebuild: the node table does not fit the mirrors' layout (%u)", err);
-        return ESC_E_HIP;
-    }
-    g_rebuild_ms[2] = (rebuild_clock() - t0) * 1e3;
-    t0 = rebuild_clock();
-    // ---- host mirrors: entry -> node in one copy, the map, allNodes[0] of every group
-    std::vector<uint32_t> h_e_node((size_t)E), ne_pos((size_t)M);
-    if (E) HIP_TRY(hipMemcpy(h_e_node.data(), b.e_node, (size_t)E * 4, hipMemcpyDeviceToHost));
-    if (M) HIP_TRY(hipMemcpy(ne_pos.data(), B.ne_pos, (size_t)M * 4, hipMemcpyDeviceToHost));
-    std::vector<GroupNode> gn((size_t)G);
-    for (int32_t g = 0; g < G; ++g) {
-        const uint32_t q = c->gi.gpair[g];
-        const bool any = L.pair_next[q] > L.pair_lo[q];
-        const uint32_t first = any ? h_e_node[L.pair_lo[q]] : NONE;      // sorted by node: the lowest
-        if (any && (int64_t)first >= N) return fail_hip(hipErrorUnknown, "nodes rebuild: entry mirror");
-        gn[g] = group_node(L, q, first, any ? c->h_ncpu[first] : 0, any ? c->h_nmem[first] : 0);
-    }
-    if (G) HIP_TRY(hipMemcpy(b.gnode, gn.data(), gn.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
-    g_rebuild_ms[3] = (rebuild_clock() - t0) * 1e3;
-    // ---- the swap: nothing below fails before the snapshot is whole again
-    drop_graphs(c);                                          // captured steps hold the old buffers
-    std::swap(c->nodes.d, B.nb);
-    std::swap(c->d_ne_off, B.ne_off); std::swap(c->d_ne_pos, B.ne_pos);
-    std::swap(c->d_nn_off, B.nn_off); std::swap(c->d_nn_list, B.nn_list);
-    if (reap) {
-        std::swap(c->d_e_pair, B.e_pair); std::swap(c->d_occ, B.occ); std::swap(c->d_occ_local, B.occ_local);
-        std::swap(c->d_rm_off, B.rm_off); std::swap(c->d_rm_list, B.rm_list);
-        c->h_rm_off = L.list_off;
-    }
-    commit_layout(c, L, pk_ok);
-    c->h_nn_new.clear();
-    c->h_e_node.swap(h_e_node);
-    ne_off.resize((size_t)N + 1);                            // the host map covers the nodes so far (adds append)
-    c->ne_off.swap(ne_off);
-    c->ne_pos.swap(ne_pos);
-    c->ne_dev_nodes = N;                                     // the device copy is the one just built
-    c->ne_dev_pos = M;
-    std::copy(nflags.begin(), nflags.end(), c->h_nflags.begin());
-    std::copy(xl_off.begin(), xl_off.begin() + NC, c->h_xl_off.begin());
-    c->h_xl.swap(h_xl);
-    c->xl_used = c->n_xl = (int64_t)xw;
-    c->xl_cap = xl_cap;
-    c->h_gnode.swap(gn);
-    c->sel_valid = c->rm_valid = c->nn_valid = false;
-    c->sorted = false;
-    // ---- what is recounted over the new entries: a failure from here on leaves the node
-    // side stale (the occupancy words) or the orderings refused (the age index), as after a load
-    t0 = rebuild_clock();
-    if (reap && c->placed)
-        if (int32_t rc = occ_recount(c)) { c->stale |= STALE_NODES; return rc; }
-    g_rebuild_ms[4] = (rebuild_clock() - t0) * 1e3;
-    t0 = rebuild_clock();
-    release_sort(c);                                         // a fresh index: regions sized from the live counts
-    const int32_t rc = build_age_index(c);
-    g_rebuild_ms[5] = (rebuild_clock() - t0) * 1e3;
-    return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t esc_nodes_rebuild(esc_ctx* c) {
-    if (c && c->multi) return esc::multi_nodes_rebuild(c);
-    if (!c) return ESC_E_INVAL;
-    if (!c->has_device) return ESC_E_NODEV;
-    if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
-    return nodes_rebuild_one(c);
-}
-
-int32_t esc_nodes_room(const esc_ctx* c, int64_t* free_slots, int64_t* free_xl_words) {
-    if (c && c->multi) return esc_nodes_room(esc::multi_sub(c, 0), free_slots, free_xl_words);
-    if (!c) return ESC_E_INVAL;
-    if (!c->has_device) return ESC_E_NODEV;
-    if (!c->nodes_loaded) return ESC_E_STATE;
-    if (free_slots) *free_slots = c->n_cap - c->n_nodes;
-    if (free_xl_words) *free_xl_words = c->xl_cap - c->xl_used;
-    return ESC_OK;
-}
-
-#if ESC_MEASURE
-// The last esc_nodes_rebuild of this thread, split (ms): host layout, upload, list + sort +
-// place, mirror download, occupancy recount, age-index build (measurement library only; not
-// in the header; scripts/rebuild_probe.py).
-int32_t esc_debug_rebuild_times(double* ms, int32_t n) {
-    if (!ms || n < 0) return ESC_E_INVAL;
-    for (int32_t k = 0; k < n && k < 6; ++k) ms[k] = g_rebuild_ms[k];
-    return ESC_OK;
-}
-#endif
-
-}  // extern "C"
-
-// ------------------------------------------------------------------- audit
-namespace {
-
-// Device scratch of one audit, freed on every way out.
-struct AuditScratch {
-    std::vector<void*> bufs;
-    ~AuditScratch() { for (void* p : bufs) hipFree(p); }
-    template <class T>
-    hipError_t get(T** p, size_t n) {
-        const hipError_t e = dalloc(p, n);
-        if (e == hipSuccess) bufs.push_back(*p);
-        return e;
-    }
-};
-
-void audit_bad(esc_audit_check& k, int64_t id) {
-    ++k.n_bad;
-    if (k.first_bad < 0 || id < k.first_bad) k.first_bad = id;
-}
-
-// TOUCH on the host (the tables are small): every column the recount `fresh` finds touched is
-// in the maintained bitmap h_touch, every workgroup's device list holds exactly its bitmap row's
-// columns, and the destinations are the columns' ranges handed out in workgroup order — what
-// touch_upload derives from the bitmap.  An offender is a (workgroup, column) pair, counted once.
-void audit_touch(const esc_ctx* c, const std::vector<uint32_t>& fresh, const std::vector<uint2>& cols,
-                 const std::vector<uint32_t>& wg_off, const std::vector<uint32_t>& col_rows, esc_audit_check& k) {
-    const int64_t nblk = c->nblk, tw = c->touch_tw, n_col = slot_stride(c) / FC_COL;
-    std::vector<uint64_t> bad;
-    auto key = [](int64_t b, int64_t col) { return ((uint64_t)b << 32) | (uint64_t)(uint32_t)col; };
-    auto kept = [&](int64_t b, int64_t col) { return (c->h_touch[b * tw + (col >> 5)] >> (col & 31)) & 1u; };
-    std::vector<uint32_t> seen(n_col, 0), stamp(n_col, 0);
-    for (int64_t b = 0; b < nblk; ++b) {
-        for (int64_t w = 0; w < tw; ++w)
-            for (uint32_t x = fresh[b * tw + w]; x; x &= x - 1) {
-                const int64_t col = w * 32 + __builtin_ctz(x);
-                if (col >= n_col) continue;
-                ++k.n_checked;
-                if (!kept(b, col)) bad.push_back(key(b, col));
-            }
-        const int64_t cnt = std::min<int64_t>(wg_off[b], n_col);
-        if ((int64_t)wg_off[b] > n_col) bad.push_back(key(b, 0xFFFFFFFFll));
-        for (int64_t i = 0; i < cnt; ++i) {
-            const uint2 e = cols[b * n_col + i];
-            if ((int64_t)e.x >= n_col) { bad.push_back(key(b, e.x)); continue; }
-            if (stamp[e.x] == (uint32_t)b + 1 || !kept(b, e.x) || e.y != col_rows[e.x] + seen[e.x]) bad.push_back(key(b, e.x));
-            if (stamp[e.x] != (uint32_t)b + 1) ++seen[e.x];
-            stamp[e.x] = (uint32_t)b + 1;
-        }
-        for (int64_t w = 0; w < tw; ++w)
-            for (uint32_t x = c->h_touch[b * tw + w]; x; x &= x - 1) {
-                const int64_t col = w * 32 + __builtin_ctz(x);
-                if (col < n_col && stamp[col] != (uint32_t)b + 1) bad.push_back(key(b, col));
-            }
-    }
-    for (int64_t col = 0; col < n_col; ++col)                  // the columns' ranges (K3 reads them)
-        if (col_rows[col + 1] - col_rows[col] != seen[col] || (col == 0 && col_rows[0] != 0)) bad.push_back(key(nblk, col));
-    std::sort(bad.begin(), bad.end());
-    bad.erase(std::unique(bad.begin(), bad.end()), bad.end());
-    for (uint64_t x : bad) audit_bad(k, (int64_t)x);
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t esc_audit(esc_ctx* c, uint32_t checks, esc_audit_report* out) {
-    if (c && c->multi) return esc::multi_audit(c, checks, out);
-    if (!c || !out || (checks >> ESC_AUD_N)) return ESC_E_INVAL;
-    if (!c->has_device) return ESC_E_NODEV;
-    if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
-    if (!checks) checks = (1u << ESC_AUD_N) - 1;
-    std::memset(out, 0, sizeof *out);
-    for (esc_audit_check& k : out->check) k.first_bad = -1;
-    // a check whose derived state is not resident is skipped: the occupancy words come with a
-    // placement, the regions with a valid age index, the touch tables with the first step's
-    // static K1 plan
-    uint32_t skip = 0;
-    if (!c->placed || !c->d_e_pair || !c->d_occ) skip |= 1u << ESC_AUD_OCC;
-    if (!(c->age_built && c->age_ok && !c->h_pcap.empty() && c->d_g_memb)) skip |= 1u << ESC_AUD_REGION;
-    if (!c->pods_loaded || !c->work_ready || !c->touch_on || !c->d_k1seg || c->pods.empty()) skip |= 1u << ESC_AUD_TOUCH;
-    out->skipped = checks & skip;
-    out->ran = checks & ~skip;
-    const uint32_t run = out->ran;
-    auto on = [&](int k) { return (run >> k) & 1u; };
-    hipSetDevice(c->device);
-    hipStream_t st = c->stream;
-    const GroupDev g = group_dev(c);
-    const NodeDev n = node_dev(c);
-    const int32_t G = c->gi.G;
-    const uint32_t n_gp = c->gi.n_gp;
-    const int64_t E = c->n_entries, NC = c->n_cap;
-    AuditScratch S;
-    AuditDev a{};
-    std::vector<int64_t> rep((size_t)ESC_AUD_N * AW_K, 0);
-    for (int k = 0; k < ESC_AUD_N; ++k) rep[(size_t)k * AW_K + AW_FIRST] = INT64_MAX;
-    HIP_TRY(S.get(&a.rep, rep.size()));
-    HIP_TRY(hipMemcpyAsync(a.rep, rep.data(), rep.size() * 8, hipMemcpyHostToDevice, st));
-    a.n_cap = NC;
-    a.n_entries = E;
-    a.e_pair = c->placed ? c->d_e_pair : nullptr;
-    std::vector<uint32_t> pair_cnt(std::max<uint32_t>(n_gp, 1), 0), memb_cnt((size_t)std::max<int32_t>(G, 1), 0);
-    std::vector<uint32_t> own;                                  // the groups whose node side this rank owns
-    for (int32_t q = 0; q < G; ++q)
-        if (owns_group(c, (uint32_t)q)) own.push_back((uint32_t)q);
-    if (on(ESC_AUD_ENTRY)) {
-        if (int32_t rc = ensure_ne_dev(c)) return rc;           // (the lazily uploaded map, re-sent when out of date)
-        a.ne_off = c->d_ne_off;
-        a.ne_pos = c->d_ne_pos;
-        a.ne_len = (int64_t)c->ne_pos.size();
-        HIP_TRY(S.get(&a.pair_cnt, pair_cnt.size()));
-        HIP_TRY(hipMemsetAsync(a.pair_cnt, 0, pair_cnt.size() * 4, st));
-        HIP_TRY(launch_audit_entries(n, g, a, st));
-        HIP_TRY(launch_audit_node_entries(n, g, a, st));
-        HIP_TRY(hipMemcpyAsync(pair_cnt.data(), a.pair_cnt, pair_cnt.size() * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (on(ESC_AUD_FIRST) && !own.empty()) {
-        uint32_t* d_own = nullptr;
-        HIP_TRY(S.get(&d_own, own.size()));
-        HIP_TRY(hipMemcpyAsync(d_own, own.data(), own.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(launch_audit_first(n, g, GroupList{d_own, (int32_t)own.size(), 0}, a, st));
-    }
-    if (on(ESC_AUD_REGION) && G > 0) {
-        uint32_t *d_ps = nullptr, *d_pl = nullptr;
-        HIP_TRY(S.get(&d_ps, (size_t)G + 1));
-        HIP_TRY(S.get(&d_pl, (size_t)G));
-        HIP_TRY(S.get(&a.memb_cnt, memb_cnt.size()));
-        HIP_TRY(hipMemcpyAsync(d_ps, c->h_pstart.data(), ((size_t)G + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_pl, c->h_plen.data(), (size_t)G * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(a.memb_cnt, 0, memb_cnt.size() * 4, st));
-        HIP_TRY(launch_audit_regions(n, g, d_ps, d_pl, c->d_g_memb, a, st));
-        HIP_TRY(hipMemcpyAsync(memb_cnt.data(), a.memb_cnt, memb_cnt.size() * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (on(ESC_AUD_OCC) && E > 0) {
-        // K6 into scratch through a view of the placement that points there, then the compare
-        uint32_t* fresh = nullptr;
-        HIP_TRY(S.get(&fresh, (size_t)(2 * E)));
-        RemovalDev r = occ_dev(c);
-        const uint32_t* kept = r.occ_pair;
-        r.occ_pair = fresh;
-        r.occ_def = fresh + E;
-        HIP_TRY(launch_occupancy(n, g, r, st));
-        HIP_TRY(launch_audit_occ(n, g, a, fresh, kept, st));
-    }
-    std::vector<uint32_t> t_fresh, t_off, t_rows;
-    std::vector<uint2> t_cols;
-    if (on(ESC_AUD_TOUCH)) {
-        const int64_t n_col = slot_stride(c) / FC_COL;
-        t_fresh.assign((size_t)c->nblk * c->touch_tw, 0);
-        t_off.assign((size_t)c->nblk, 0);
-        t_rows.assign((size_t)n_col + 1, 0);
-        t_cols.assign((size_t)c->nblk * n_col, make_uint2(0, 0));
-        uint32_t* d_bits = nullptr;
-        HIP_TRY(S.get(&d_bits, t_fresh.size()));
-        HIP_TRY(launch_touch(pod_dev(c, 0), g, c->nblk, c->touch_tw, d_bits, st));
-        HIP_TRY(hipMemcpyAsync(t_fresh.data(), d_bits, t_fresh.size() * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(t_off.data(), c->d_wg_off, t_off.size() * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(t_rows.data(), c->d_col_rows, t_rows.size() * 4, hipMemcpyDeviceToHost, st));
-        if (!t_cols.empty())
-            HIP_TRY(hipMemcpyAsync(t_cols.data(), c->d_wg_cols, t_cols.size() * sizeof(uint2), hipMemcpyDeviceToHost, st));
-    }
-    if (on(ESC_AUD_TRACKER)) HIP_TRY(launch_audit_tracker(n, g, a, st));
-    std::vector<uint32_t> m_flags, m_label0;
-    std::vector<int64_t> m_cpu, m_mem;
-    if (on(ESC_AUD_MIRROR) && NC > 0) {
-        m_flags.resize(NC); m_label0.resize(NC); m_cpu.resize(NC); m_mem.resize(NC);
-        HIP_TRY(hipMemcpyAsync(m_flags.data(), c->nodes.flags, NC * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(m_label0.data(), c->nodes.label0, NC * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(m_cpu.data(), c->nodes.cpu, NC * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(m_mem.data(), c->nodes.mem, NC * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(rep.data(), a.rep, rep.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k < ESC_AUD_N; ++k) {
-        esc_audit_check& x = out->check[k];
-        x.n_checked = rep[(size_t)k * AW_K + AW_CHECKED];
-        x.n_bad = rep[(size_t)k * AW_K + AW_BAD];
-        x.first_bad = x.n_bad ? rep[(size_t)k * AW_K + AW_FIRST] : -1;
-    }
-    if (on(ESC_AUD_ENTRY))                                      // per-pair live counts against the host's
-        for (uint32_t q = 0; q < n_gp; ++q)
-            if ((int64_t)pair_cnt[q] != c->pair_live[q]) audit_bad(out->check[ESC_AUD_ENTRY], c->pair_lo[q]);
-    if (on(ESC_AUD_REGION))                                     // a group's live memberships = its pair's live entries
-        for (uint32_t q : own)
-            if ((int64_t)memb_cnt[q] != c->pair_live[c->gi.gpair[q]]) audit_bad(out->check[ESC_AUD_REGION], c->h_pstart[q]);
-    if (on(ESC_AUD_TOUCH)) audit_touch(c, t_fresh, t_cols, t_off, t_rows, out->check[ESC_AUD_TOUCH]);
-    if (on(ESC_AUD_MIRROR)) {
-        esc_audit_check& x = out->check[ESC_AUD_MIRROR];
-        x.n_checked = NC;
-        for (int64_t j = 0; j < NC; ++j)
-            if (m_flags[j] != c->h_nflags[j] || m_cpu[j] != c->h_ncpu[j] || m_mem[j] != c->h_nmem[j] ||
-                m_label0[j] != c->h_label0[j])
-                audit_bad(x, j);
-    }
-    return ESC_OK;
-}
-
-#if ESC_MEASURE
-// Corruption injection (measurement library only; not in the header; tests/audit_child.py): one
-// derived word made wrong, so that a test can show the matching audit check sees it.  Only
-// VALUE words are reachable — no kernel uses one of them as an address, index, offset, length
-// or loop bound — so a poke changes numbers, never where a kernel reads or writes:
-//   0 entry `index`: its UNSCHED / TAINTED bits ^= value (1..3)   1 entry: e_cpu (and the packed copy) = value
-//   2 region word `index`: UNSCHED / TAINTED / TRACKED of its nibble ^= value (1..7)
-//   3 region words `index`, `index` + 1 swapped (two memberships of one group)
-//   4 occupancy word `index` of [2][n_entries] = value       5 touch bitmap: workgroup `index`, set column `value` cleared
-//   6 node `index`: ESC_NF_TRACKED flipped in the device node table only
-//   7 group `index`: GroupNode::first_cpu = value            8 node `index`: the host mirror h_ncpu = value
-// Everything else is ESC_E_INVAL.
-int32_t esc_debug_poke(esc_ctx* c, int32_t what, int64_t index, int64_t value) {
-    if (!c || c->multi || index < 0) return ESC_E_INVAL;
-    if (!c->has_device) return ESC_E_NODEV;
-    if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
-    hipSetDevice(c->device);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    auto live_entry = [&](int64_t e) {                         // an entry of a group pair whose node is live
-        return e < c->n_entries && c->h_e_node[e] != NONE && !(c->h_nflags[c->h_e_node[e]] & ESC_NF_ABSENT) &&
-               entry_pair(c, (uint32_t)e) != NONE;
-    };
-    // the owned group whose live memberships hold region word i (h_pstart / h_plen), or -1
-    auto region_group = [&](int64_t i) -> int32_t {
-        if (!(c->age_built && c->age_ok) || c->h_pstart.empty()) return -1;
-        for (int32_t q = 0; q < c->gi.G; ++q)
-            if (owns_group(c, (uint32_t)q) && i >= c->h_pstart[q] && i < (int64_t)c->h_pstart[q] + c->h_plen[q]) return q;
-        return -1;
-    };
-    uint32_t w = 0, w2 = 0;
-    switch (what) {
-    case 0:
-        if (!live_entry(index) || value < 1 || value > 3) return ESC_E_INVAL;
-        HIP_TRY(hipMemcpy(&w, c->nodes.d.e_flags + index, 4, hipMemcpyDeviceToHost));
-        w ^= (uint32_t)value;
-        HIP_TRY(hipMemcpy(c->nodes.d.e_flags + index, &w, 4, hipMemcpyHostToDevice));
-        return ESC_OK;
-    case 1:
-        if (!live_entry(index) || !entry_cpu_packs(value)) return ESC_E_INVAL;
-        w = (uint32_t)value;
-        HIP_TRY(hipMemcpy(c->nodes.d.e_cpu + index, &value, 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(reinterpret_cast<uint32_t*>(c->nodes.d.e_pk + index) + 1, &w, 4, hipMemcpyHostToDevice));
-        return ESC_OK;
-    case 2:
-        if (region_group(index) < 0 || value < 1 || value > 7) return ESC_E_INVAL;
-        HIP_TRY(hipMemcpy(&w, c->d_g_memb + index, 4, hipMemcpyDeviceToHost));
-        w ^= (uint32_t)value << MEMB_FLAG_SHIFT;
-        HIP_TRY(hipMemcpy(c->d_g_memb + index, &w, 4, hipMemcpyHostToDevice));
-        return ESC_OK;
-    case 3:
-        if (region_group(index) < 0 || region_group(index) != region_group(index + 1)) return ESC_E_INVAL;
-        HIP_TRY(hipMemcpy(&w, c->d_g_memb + index, 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&w2, c->d_g_memb + index + 1, 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(c->d_g_memb + index, &w2, 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_g_memb + index + 1, &w, 4, hipMemcpyHostToDevice));
-        return ESC_OK;
-    case 4: {
-        uint32_t* o = c->d_occ_local ? c->d_occ_local : c->d_occ;
-        if (!c->placed || !o || index >= 2 * c->n_entries || value < 0 || value > (int64_t)0xFFFFFFFF) return ESC_E_INVAL;
-        if (!live_entry(index % c->n_entries)) return ESC_E_INVAL;   // a word K7 reads
-        w = (uint32_t)value;
-        HIP_TRY(hipMemcpy(o + index, &w, 4, hipMemcpyHostToDevice));
-        return ESC_OK;
-    }
-    case 5:
-        if (!c->touch_on || index >= c->nblk || value < 0 || value >= slot_stride(c) / FC_COL) return ESC_E_INVAL;
-        if (!((c->h_touch[(size_t)index * c->touch_tw + (size_t)(value >> 5)] >> (value & 31)) & 1u)) return ESC_E_INVAL;
-        c->h_touch[(size_t)index * c->touch_tw + (size_t)(value >> 5)] &= ~(1u << (value & 31));
-        return ESC_OK;
-    case 6:
-        if (index >= c->n_nodes || (c->h_nflags[index] & ESC_NF_ABSENT)) return ESC_E_INVAL;
-        HIP_TRY(hipMemcpy(&w, c->nodes.flags + index, 4, hipMemcpyDeviceToHost));
-        w ^= ESC_NF_TRACKED;
-        HIP_TRY(hipMemcpy(c->nodes.flags + index, &w, 4, hipMemcpyHostToDevice));
-        return ESC_OK;
-    case 7:
-        if (index >= c->gi.G) return ESC_E_INVAL;
-        HIP_TRY(hipMemcpy(&c->nodes.d.gnode[index].first_cpu, &value, 8, hipMemcpyHostToDevice));
-        return ESC_OK;
-    case 8:
-        if (index >= c->n_nodes || (c->h_nflags[index] & ESC_NF_ABSENT)) return ESC_E_INVAL;
-        c->h_ncpu[index] = value;
-        return ESC_OK;
-    default:
-        return ESC_E_INVAL;
-    }
-}
-#endif
 
 // ----------------------------------------------------------------- ordering
 int32_t esc_sort_nodes(esc_ctx* c) {

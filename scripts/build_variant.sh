@@ -10,10 +10,14 @@ HIPCC=/opt/rocm/bin/hipcc
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result -I../../include -I."
 $HIPCC $FL "$@" -DESC_PART=0 -c esc_kernels.hip -o $B/esc_kernels.o
 O=../../build/csrc
-RT=$O/esc_runtime.o
+# the host runtime's files (the Makefile's SRCS_RT)
+RT_SRCS="esc_runtime esc_rebuild"
+RT_DIR=$O
 if [ -n "$REBUILD_RT" ]; then            # flags that change the runtime's view too (e.g. -DESC_ORD_CHUNK)
-    $HIPCC $FL "$@" -c esc_runtime.hip -o $B/esc_runtime.o
-    RT=$B/esc_runtime.o
+    for f in $RT_SRCS; do $HIPCC $FL "$@" -c $f.hip -o $B/$f.o; done
+    RT_DIR=$B
 fi
+RT=""
+for f in $RT_SRCS; do RT="$RT $RT_DIR/$f.o"; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libescalator_hip_$NAME.so $B/esc_kernels.o $RT \
     $O/esc_multi.o $O/esc_list.o $O/esc_pack.o $O/esc_synth.o -pthread
