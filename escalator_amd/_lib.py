@@ -191,6 +191,7 @@ _SIGS = {
     "esc_nodes_relabel": (i32, [VP, P(i64), P(NodeSoA)]),
     "esc_nodes_rebuild": (i32, [VP]),
     "esc_nodes_room": (i32, [VP, P(i64), P(i64)]),
+    "esc_nodes_compact": (i32, [VP, i64, i64, P(i64), i64]),
     "esc_hbm_probe": (i32, [VP, i64, i32, P(C.c_double)]),
     "esc_tracker_update": (i32, [VP, i32, P(i64), i64, P(i64), i64]),
     "esc_tracker_list": (i32, [VP, i32, P(i64), i64, P(i64)]),

@@ -323,9 +323,24 @@ class Context:
         ``nodes_room()`` shows free table slots."""
         L.check(self.lib.esc_nodes_rebuild(self.handle), "esc_nodes_rebuild")
 
+    def nodes_compact(self, min_free_slots: int = 0, min_free_xl_words: int = 0) -> np.ndarray:
+        """The node table compacted and grown on the device (esc_nodes_compact): the live nodes
+        renumbered densely in snapshot order into a table with fresh free slots (at least
+        `min_free_slots`) and extra-label room (at least `min_free_xl_words`), the placement's
+        runs re-cut, the node side derived as nodes_rebuild does; no pod is read or written.
+        Returns new_index: the new index of every old slot, -1 for a deleted one.  The answer
+        to an ESC_E_LIMIT that ``nodes_room()`` shows to be a lack of table slots, and to a
+        pods_bind into a full run."""
+        a, b = C.c_int64(), C.c_int64()
+        L.check(self.lib.esc_ctx_counts(self.handle, C.byref(a), C.byref(b)), "esc_ctx_counts")
+        out = np.zeros(max(b.value, 1), np.int64)
+        L.check(self.lib.esc_nodes_compact(self.handle, int(min_free_slots), int(min_free_xl_words),
+                                           out.ctypes.data_as(C.POINTER(C.c_int64)), b.value), "esc_nodes_compact")
+        return out[:b.value]
+
     def nodes_room(self) -> tuple[int, int]:
         """(free node-table slots, free extra-label words): a rebuild does not grow the table,
-        so an add of more nodes than the free slots still needs a full load."""
+        so an add of more nodes than the free slots needs nodes_compact."""
         a, b = C.c_int64(), C.c_int64()
         L.check(self.lib.esc_nodes_room(self.handle, C.byref(a), C.byref(b)), "esc_nodes_room")
         return a.value, b.value

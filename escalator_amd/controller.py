@@ -465,18 +465,26 @@ class ResidentController(Controller):
     (``events.rebuild_causes``), and so is an audit mismatch confined to the state a rebuild
     re-derives (ENTRY, FIRST, REGION, OCC, TRACKER): those checks are run again after it, and
     only a mismatch that survives — or one in TOUCH or MIRROR — reloads.  The trackers outlive
-    a rebuild, so nothing is re-added after one."""
+    a rebuild, so nothing is re-added after one.
+
+    ``node_compact=True`` (implies the rule above): a ``nodes_add`` that finds too few free
+    table slots, and a ``pods_bind`` into a full run, are answered by ``ctx.nodes_compact()`` and
+    one retry (``events.compact_causes``).  The node indices change with it; the tracker lists
+    and instantiation times here are keyed by name, and the tracker pass that follows finds
+    nothing missing."""
 
     REBUILT_CHECKS = ("ENTRY", "FIRST", "REGION", "OCC", "TRACKER")
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
-                 selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0, node_rebuild: bool = False):
+                 selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0, node_rebuild: bool = False,
+                 node_compact: bool = False):
         super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
                          selection_slack=selection_slack)
         from .events import EventQueue
         self.spare = float(spare)
-        self.node_rebuild = bool(node_rebuild)
-        self.events = EventQueue(spare=self.spare, rebuild=self.node_rebuild)
+        self.node_compact = bool(node_compact)
+        self.node_rebuild = bool(node_rebuild) or self.node_compact
+        self.events = EventQueue(spare=self.spare, rebuild=self.node_rebuild, compact=self.node_compact)
         # the resync of the derived state (the reference's informers resync hourly,
         # pkg/k8s/cache.go:27,48): every audit_every-th scan audits the snapshot after the flush
         # and reloads it once when a check finds a mismatch; 0 = never

@@ -1,7 +1,7 @@
 // esc_ctx.h — the context behind the C ABI, private to the host runtime's files:
 //   esc_runtime.hip   the context, the decision step, the loaders, the ordering, the events,
 //                     reaping
-//   esc_rebuild.hip   the device rebuild of the node side, the audit
+//   esc_rebuild.hip   the device rebuild of the node side, the node table's compaction, the audit
 // Everything else (esc_multi.hip, esc_list.hip, the packer, the generator) sees esc_ctx as
 // opaque.  Helpers that cross a file are declared at the end, each defined in the file of its
 // subsystem; the small ones are inline here.
@@ -383,6 +383,29 @@ inline uint32_t entry_pair(const esc_ctx* c, uint32_t e) {
     if (!n_gp || e >= c->pair_end[n_gp - 1]) return NONE;
     const uint32_t q = (uint32_t)(std::upper_bound(c->pair_lo.begin(), c->pair_lo.end(), e) - c->pair_lo.begin()) - 1;
     return e < c->pair_end[q] ? q : NONE;
+}
+
+// Host threads for the load-time layout passes: ESC_HOST_THREADS, else OMP_NUM_THREADS (the
+// GPU box sets 16, its CPU share per GPU), else min(16, hardware threads).
+inline int host_threads() {
+    int n = 0;
+    for (const char* e : {"ESC_HOST_THREADS", "OMP_NUM_THREADS"})
+        if (const char* v = std::getenv(e)) { n = std::atoi(v); if (n > 0) break; }
+    if (n <= 0) n = std::min<int>(16, std::max(1u, std::thread::hardware_concurrency()));
+    return std::max(1, std::min(n, 64));
+}
+
+// f(t, lo, hi) over T contiguous chunks of [0, n), one host thread each (in order for T = 1)
+template <class F>
+void par_chunks(int64_t n, int T, F&& f) {
+    if (T <= 1 || n < 4096) {
+        f(0, (int64_t)0, n);
+        return;
+    }
+    std::vector<std::thread> th;
+    th.reserve(T);
+    for (int t = 0; t < T; ++t) th.emplace_back([&, t] { f(t, n * t / T, n * (t + 1) / T); });
+    for (auto& x : th) x.join();
 }
 
 // ---- esc_runtime.hip

@@ -691,6 +691,32 @@ struct RebuildDev {
 // pair_bits: bits of the largest resident pair id (one 8-bit pass per started byte).
 hipError_t launch_nodes_rebuild(const RebuildDev& r, uint64_t* elems[2], uint32_t* hist, uint32_t* tot, int pair_bits,
                                 hipStream_t st);
+// esc_nodes_compact: the live nodes gathered into a new table in the host's order (k_node_gather,
+// one thread per new slot) and every live node's PodRefs moved to its re-cut run (k_run_move,
+// one wave per non-empty run).  Everything marked "plan" is host-made and uploaded; nothing is
+// written in place.  A source slot or a run that does not fit the buffers sets *err (the
+// rebuild's error word) and indexes nothing.
+struct CompactDev {
+    // the old table and its per-node facts (read); taint_s / no_delete: null without a placement
+    const uint32_t *flags, *label0, *xl_off;
+    const int64_t *cpu, *mem, *created, *inst, *taint_s;
+    const uint8_t* no_delete;
+    int64_t n_old;                         // old n_nodes: the slots a source may name
+    // plan
+    const uint32_t* src_of;                // [n_new] old slot of every new one (NONE: free)
+    int64_t n_new;                         // the new capacity
+    const uint32_t* moves;                 // [n_moves][3] old PodRef offset, new offset, length
+    int64_t n_moves;
+    // built
+    uint32_t *flags_new, *label0_new, *xl_off_new;   // xl_off_new: the OLD offsets, by new slot
+    int64_t *cpu_new, *mem_new, *created_new, *inst_new, *taint_new;
+    uint8_t* nd_new;
+    const uint32_t* refs_old;              // the PodRef buffers as 4-byte words
+    uint32_t* refs_new;
+    int64_t refs_old_words, refs_new_words;
+    uint32_t* err;
+};
+hipError_t launch_nodes_compact(const CompactDev& c, hipStream_t st);
 // The bounded waits of the decoupled look-backs (k_ord_split, k_memb_keys): HIP does not
 // promise dispatch order, so a chunk never waits unboundedly on one that was not dispatched.
 // A chunk that waited `spins` probes gives up: it publishes a FAILED status word (never an

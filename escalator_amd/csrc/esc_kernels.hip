@@ -3581,7 +3581,73 @@ __global__ __launch_bounds__(256) void k_entry_place(RebuildDev R, const uint64_
     R.ne_pos[a + slot] = (uint32_t)e;
 }
 
+// ===================================================================== node-table compaction
+// esc_nodes_compact (CompactDev, esc_kernels.h): the host's plan names every source and every
+// destination, the old buffers are only read and the new ones only written.
+namespace {
+constexpr uint32_t CP_ERR_SRC = 16u, CP_ERR_RUN = 32u;
+}  // namespace
+
+// One thread per NEW table slot: src_of streamed coalesced (it ascends, so neighbouring lanes
+// gather from neighbouring or nearby old slots), the node's columns and per-node facts moved
+// to the slot, a free slot left as a load leaves it.  A source outside the old table or one
+// that names an absent slot is reported and the slot written as a free one.
+__global__ __launch_bounds__(256) void k_node_gather(CompactDev C) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= C.n_new) return;
+    uint32_t s = C.src_of[i];
+    uint32_t f = ESC_NF_ABSENT;
+    if (s != NONE) {
+        if ((int64_t)s >= C.n_old) {
+            rb_fail(C.err, CP_ERR_SRC);
+            s = NONE;
+        } else {
+            f = C.flags[s];
+            if (f & ESC_NF_ABSENT) {
+                rb_fail(C.err, CP_ERR_SRC);
+                s = NONE;
+                f = ESC_NF_ABSENT;
+            }
+        }
+    }
+    const bool on = s != NONE;
+    C.flags_new[i] = f;
+    C.label0_new[i] = on ? C.label0[s] : NONE;
+    C.cpu_new[i] = on ? C.cpu[s] : 0;
+    C.mem_new[i] = on ? C.mem[s] : 0;
+    C.created_new[i] = on ? C.created[s] : 0;
+    C.xl_off_new[i] = on ? C.xl_off[s] : 0u;
+    C.inst_new[i] = on ? C.inst[s] : INT64_MIN;
+    if (C.taint_new) {
+        C.taint_new[i] = on ? C.taint_s[s] : INT64_MIN;
+        C.nd_new[i] = on ? C.no_delete[s] : (uint8_t)0;
+    }
+}
+
+// One wave per live node with a non-empty run: its PodRefs copied as a flat stream of 4-byte
+// words, lane-strided (a PodRef is 20 B and the runs start anywhere: no wider access is
+// aligned at both ends).  A move that leaves either buffer is reported and copies nothing.
+__global__ __launch_bounds__(256) void k_run_move(CompactDev C) {
+    const int64_t m = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (m >= C.n_moves) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t src = (int64_t)C.moves[3 * m] * 5, dst = (int64_t)C.moves[3 * m + 1] * 5;
+    const int64_t words = (int64_t)C.moves[3 * m + 2] * 5;
+    if (src + words > C.refs_old_words || dst + words > C.refs_new_words) {
+        if (lane == 0) rb_fail(C.err, CP_ERR_RUN);
+        return;
+    }
+    for (int64_t k = lane; k < words; k += 64) C.refs_new[dst + k] = C.refs_old[src + k];
+}
+
 // ===================================================================== launchers
+hipError_t launch_nodes_compact(const CompactDev& c, hipStream_t st) {
+    static_assert(sizeof(PodRef) == 20, "k_run_move copies a PodRef as five words");
+    if (c.n_new > 0) hipLaunchKernelGGL(k_node_gather, dim3((unsigned)((c.n_new + 255) / 256)), dim3(256), 0, st, c);
+    if (c.n_moves > 0) hipLaunchKernelGGL(k_run_move, dim3((unsigned)((c.n_moves + 3) / 4)), dim3(256), 0, st, c);
+    return hipGetLastError();
+}
+
 hipError_t launch_pod_bigtiles(const PodDev& p, const GroupDev& g, const uint32_t* tiles, int64_t n_big,
                                int64_t* wide, hipStream_t st) {
     if (n_big <= 0) return hipSuccess;

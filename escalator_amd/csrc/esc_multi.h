@@ -71,6 +71,8 @@ int32_t multi_audit(esc_ctx* c, uint32_t checks, esc_audit_report* out);        
 int32_t multi_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out);
 int32_t multi_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_nodes_rebuild(esc_ctx* c);                                          // every device's node side (esc_nodes_rebuild)
+int32_t multi_nodes_compact(esc_ctx* c, int64_t min_free_slots, int64_t min_free_xl_words, int64_t* new_index,
+                            int64_t cap);                                        // every device's table (esc_nodes_compact)
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s);
 int32_t multi_tracker_update(esc_ctx* c, int32_t group, const int64_t* add, int64_t n_add, const int64_t* rm,
                              int64_t n_rm);

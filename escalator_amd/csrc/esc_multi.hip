@@ -526,6 +526,23 @@ int32_t multi_nodes_rebuild(esc_ctx* c) {
     return node_event(c, [&](int i) { return esc_nodes_rebuild(M(c).subs[i]); });
 }
 
+// Every device compacts its own copy of the node table (esc_nodes_compact): the map depends on
+// that table alone, so every device must produce the same one; a device whose map differs has
+// diverged, as a device that failed.
+int32_t multi_nodes_compact(esc_ctx* c, int64_t min_free_slots, int64_t min_free_xl_words, int64_t* new_index, int64_t cap) {
+    if (min_free_slots < 0 || min_free_xl_words < 0 || cap < 0 || (cap > 0 && !new_index)) return ESC_E_INVAL;
+    int64_t np = 0, n0 = 0;
+    if (int32_t rc = esc_ctx_counts(M(c).subs[0], &np, &n0)) return rc;
+    if (cap < n0) return ESC_E_LIMIT;
+    std::vector<int64_t> tmp((size_t)std::max<int64_t>(n0, 1));
+    return node_event(c, [&](int i) {
+        int64_t* out = i == 0 ? new_index : tmp.data();
+        const int32_t rc = esc_nodes_compact(M(c).subs[i], min_free_slots, min_free_xl_words, out, n0);
+        if (rc == ESC_OK && i > 0 && n0 > 0 && std::memcmp(out, new_index, (size_t)n0 * 8) != 0) return (int32_t)ESC_E_STATE;
+        return rc;
+    });
+}
+
 int32_t multi_tracker_update(esc_ctx* c, int32_t group, const int64_t* add, int64_t n_add, const int64_t* rm,
                              int64_t n_rm) {
     return node_event(c, [&](int i) { return esc_tracker_update(M(c).subs[i], group, add, n_add, rm, n_rm); });

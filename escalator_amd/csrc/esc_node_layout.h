@@ -2,8 +2,10 @@
 //
 // esc_load_nodes and esc_nodes_rebuild lay the pair-major entries out from the same counts,
 // and everything downstream (K2, k_node_groups, k_entry_fill, the audit, the event patches)
-// rests on their agreeing: the rules live here and nowhere else.  Host only, plain C++17, no
-// HIP header: tests/node_layout_check.cpp builds it with the host compiler.
+// rests on their agreeing: the rules live here and nowhere else.  So do the capacity rule of
+// the placement's runs (esc_load_placement, esc_nodes_compact) and the compaction's plan.
+// Host only, plain C++17, no HIP header: tests/node_layout_check.cpp and
+// tests/node_compact_check.cpp build it with the host compiler.
 #pragma once
 
 #include <algorithm>
@@ -127,6 +129,85 @@ inline GroupNode group_node(const NodeLayout& L, uint32_t q, uint32_t first, int
     x.first_cpu = any ? cpu : 0;
     x.first_mem = any ? mem : 0;
     return x;
+}
+
+// ---- the placement's runs of PodRefs (esc_load_placement, esc_nodes_compact)
+// Room for pods bound later (esc_set_spare's fraction f; none at f = 0): a slot of the node
+// table gets its own count with the spare fraction on top, and at least the mean pods per live
+// node with the spare fraction on top (run_cap_new) — what a lightly loaded node, or a free
+// slot with no node yet, gets; the scheduler fills those.
+inline uint64_t run_cap_new(int64_t bound, int64_t live, double f) {
+    return f > 0 ? (uint64_t)std::ceil((double)bound / (double)std::max<int64_t>(live, 1) * (1.0 + f)) + 4 : 0;
+}
+inline uint64_t run_capacity(uint64_t len, bool in_table, uint64_t cap_new, double f) {
+    const uint64_t own = len + (f > 0 ? (uint64_t)std::ceil((double)len * f) + 2 : 0);
+    return in_table ? std::max(own, cap_new) : cap_new;
+}
+// The runs' offsets off[n_slots + 1] from their lengths: slots [0, n_table) hold nodes, the
+// rest are free.  ESC_E_LIMIT when the PodRefs do not fit 32-bit offsets.
+inline int32_t plan_runs(std::vector<uint32_t>& off, const uint32_t* len, int64_t n_slots, int64_t n_table, int64_t bound,
+                         int64_t live, double f) {
+    const uint64_t cap_new = run_cap_new(bound, live, f);
+    off.assign((size_t)n_slots + 1, 0);
+    uint64_t at = 0;
+    for (int64_t j = 0; j < n_slots; ++j) {
+        at += run_capacity(j < n_table ? len[j] : 0, j < n_table, cap_new, f);
+        if (at >= 0xFFFFFFFFull) return ESC_E_LIMIT;
+        off[j + 1] = (uint32_t)at;
+    }
+    return ESC_OK;
+}
+
+// ---- esc_nodes_compact: the live nodes renumbered densely, in ascending old
+// index, into a table with fresh capacity, and the placement's runs re-cut for the new table.
+constexpr int64_t NODE_INDEX_LIMIT = (int64_t)1 << 28;    // the age index's node field (MEMB_NODE_MASK)
+struct RunMove { uint32_t src, dst, len; };                // PodRef offsets in the old and new buffer
+struct CompactPlan {
+    std::vector<uint32_t> new_of;                          // [old n_nodes] new index (NONE: absent)
+    std::vector<uint32_t> src_of;                          // [n_cap] old index (NONE: a free slot)
+    int64_t n_live = 0, n_cap = 0, xl_words = 0, xl_cap = 0;
+    // with a placement: the new runs, the non-empty live runs' moves, the pods of dead runs
+    std::vector<uint32_t> run_off, run_len;                // [n_cap + 1], [n_cap]
+    std::vector<RunMove> moves;
+    std::vector<int32_t> unbind;
+    int64_t bound = 0;                                     // pods bound to live nodes
+};
+// nflags / label0: the mirrors of the old table's n_nodes slots.  run_off / run_len / run_pod:
+// the placement's mirror (null without one).  ESC_E_INVAL for a negative minimum, ESC_E_LIMIT
+// when the new table reaches NODE_INDEX_LIMIT slots or the labels or PodRefs 32-bit offsets.
+inline int32_t plan_node_compact(CompactPlan& P, const uint32_t* nflags, const uint32_t* label0, int64_t n_nodes, double f,
+                                 int64_t min_free_slots, int64_t min_free_xl_words, const uint32_t* run_off,
+                                 const uint32_t* run_len, const int32_t* run_pod) {
+    P = CompactPlan();
+    if (min_free_slots < 0 || min_free_xl_words < 0 || n_nodes < 0) return ESC_E_INVAL;
+    P.new_of.assign((size_t)n_nodes, NONE);
+    for (int64_t j = 0; j < n_nodes; ++j) {
+        if (nflags[j] & ESC_NF_ABSENT) continue;
+        P.new_of[j] = (uint32_t)P.n_live++;
+        if (label0[j] != NONE) P.xl_words += nf_xlbl(nflags[j]);
+    }
+    const int64_t L = P.n_live;
+    if (min_free_slots >= NODE_INDEX_LIMIT || min_free_xl_words >= (int64_t)0xFFFFFFFF) return ESC_E_LIMIT;
+    P.n_cap = std::max(table_slots(L, f), L + min_free_slots);
+    P.xl_cap = std::max(label_words(P.xl_words, f), P.xl_words + min_free_xl_words);
+    if (P.n_cap >= NODE_INDEX_LIMIT || P.xl_cap >= (int64_t)0xFFFFFFFF) return ESC_E_LIMIT;
+    P.src_of.assign((size_t)P.n_cap, NONE);
+    for (int64_t j = 0; j < n_nodes; ++j)
+        if (P.new_of[j] != NONE) P.src_of[P.new_of[j]] = (uint32_t)j;
+    if (!run_off) return ESC_OK;
+    P.run_len.assign((size_t)std::max<int64_t>(P.n_cap, 1), 0);
+    for (int64_t j = 0; j < n_nodes; ++j) {
+        if (P.new_of[j] != NONE) {
+            P.run_len[P.new_of[j]] = run_len[j];
+            P.bound += run_len[j];
+        } else {
+            for (uint32_t k = 0; k < run_len[j]; ++k) P.unbind.push_back(run_pod[run_off[j] + k]);
+        }
+    }
+    if (const int32_t rc = plan_runs(P.run_off, P.run_len.data(), P.n_cap, L, P.bound, L, f)) return rc;
+    for (int64_t j = 0; j < n_nodes; ++j)
+        if (P.new_of[j] != NONE && run_len[j]) P.moves.push_back(RunMove{run_off[j], P.run_off[P.new_of[j]], run_len[j]});
+    return ESC_OK;
 }
 
 }  // namespace esc

@@ -1,5 +1,7 @@
-// esc_rebuild.hip — the node-side rebuild on the device, and esc_audit with
-// the measurement library's esc_debug_poke.
+// esc_rebuild.hip — the node-side rebuild on the device, the node table's
+// compaction in front of it (§8l), and esc_audit with the measurement library's esc_debug_poke.
+#include <functional>
+
 #include "esc_ctx.h"
 
 using namespace esc;
@@ -32,12 +34,41 @@ double rebuild_clock() {
 }
 thread_local double g_rebuild_ms[6];              // host layout, upload, kernels, mirrors, occupancy, age index
 
-int32_t nodes_rebuild_one(esc_ctx* c) {
+// The node table a rebuild derives the node side from: the resident one (esc_nodes_rebuild), or
+// the one a compaction built beside it (esc_nodes_compact), whose `commit` makes it the
+// resident one at the swap.  The extra labels are always the resident words: a compacted
+// table's xl_off holds its nodes' OLD offsets.
+struct NodeSrc {
+    uint32_t* flags = nullptr;                                // device columns, [n_cap]
+    const uint32_t *label0 = nullptr, *xl_off = nullptr;
+    const int64_t *cpu = nullptr, *mem = nullptr;
+    int64_t n_nodes = 0, n_cap = 0, min_free_xl = 0;
+    const std::vector<uint32_t> *nflags = nullptr, *hlabel0 = nullptr, *hxl_off = nullptr;   // their mirrors
+    const std::vector<int64_t> *ncpu = nullptr, *nmem = nullptr;
+    const std::vector<uint64_t>* trk = nullptr;
+    std::function<void()> commit;                             // nothing in it fails
+};
+
+NodeSrc resident_src(esc_ctx* c) {
+    NodeSrc S;
+    S.flags = c->nodes.flags; S.label0 = c->nodes.label0; S.xl_off = c->nodes.d.xl_off;
+    S.cpu = c->nodes.cpu; S.mem = c->nodes.mem;
+    S.n_nodes = c->n_nodes; S.n_cap = c->n_cap;
+    S.nflags = &c->h_nflags; S.hlabel0 = &c->h_label0; S.hxl_off = &c->h_xl_off;
+    S.ncpu = &c->h_ncpu; S.nmem = &c->h_nmem; S.trk = &c->h_trk;
+    return S;
+}
+
+int32_t nodes_rebuild_from(esc_ctx* c, const NodeSrc& S) {
     const uint32_t n_gp = c->gi.n_gp;
     const int32_t G = c->gi.G;
-    const int64_t N = c->n_nodes, NC = c->n_cap;
+    const int64_t N = S.n_nodes, NC = S.n_cap;
     const double sf = c->spare_frac;
-    if ((int64_t)c->h_nflags.size() < NC || (int64_t)c->pair_live.size() != (int64_t)n_gp) return ESC_E_STATE;
+    const std::vector<uint32_t>&s_flags = *S.nflags, &s_label0 = *S.hlabel0, &s_xl_off = *S.hxl_off;
+    const std::vector<int64_t>&s_cpu = *S.ncpu, &s_mem = *S.nmem;
+    if ((int64_t)s_flags.size() < NC || (int64_t)s_label0.size() < NC || (int64_t)s_xl_off.size() < NC ||
+        (int64_t)s_cpu.size() < NC || (int64_t)s_mem.size() < NC || (int64_t)c->pair_live.size() != (int64_t)n_gp)
+        return ESC_E_STATE;
     hipSetDevice(c->device);
     HIP_TRY(hipStreamSynchronize(c->stream));
     double t0 = rebuild_clock();
@@ -45,12 +76,12 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
     // ---- the layout, from the host's counts alone
     // the tracker index and bit first: the entries carry the bit
     std::vector<uint32_t> trk_start((size_t)std::max<int64_t>(NC, 1), NONE);
-    for (int64_t k = (int64_t)c->h_trk.size() - 1; k >= 0; --k) {
-        const uint64_t j = c->h_trk[k] >> 32;
+    for (int64_t k = (int64_t)S.trk->size() - 1; k >= 0; --k) {
+        const uint64_t j = (*S.trk)[k] >> 32;
         if ((int64_t)j >= N) return fail_hip(hipErrorUnknown, "nodes rebuild: tracker mirror");
         trk_start[j] = (uint32_t)k;
     }
-    std::vector<uint32_t> nflags(c->h_nflags.begin(), c->h_nflags.begin() + NC);
+    std::vector<uint32_t> nflags(s_flags.begin(), s_flags.begin() + NC);
     std::vector<uint32_t> ne_off((size_t)NC + 1, 0), xl_off((size_t)std::max<int64_t>(NC, 1), 0);
     uint64_t m = 0, xw = 0;
     uint32_t max_pair = 0;
@@ -61,11 +92,11 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
         uint32_t& f = nflags[i];
         if (i >= N || (f & ESC_NF_ABSENT)) continue;
         f = (f & ~ESC_NF_TRACKED) | (trk_start[i] != NONE ? ESC_NF_TRACKED : 0u);
-        pk_ok = pk_ok && entry_cpu_packs(c->h_ncpu[i]);
-        if (c->h_label0[i] == NONE) continue;
+        pk_ok = pk_ok && entry_cpu_packs(s_cpu[i]);
+        if (s_label0[i] == NONE) continue;
         const uint32_t nx = nf_xlbl(f);
-        if ((uint64_t)c->h_xl_off[i] + nx > c->h_xl.size()) return fail_hip(hipErrorUnknown, "nodes rebuild: label mirror");
-        max_pair = std::max(max_pair, nx ? c->h_xl[c->h_xl_off[i] + nx - 1] : c->h_label0[i]);
+        if ((uint64_t)s_xl_off[i] + nx > c->h_xl.size()) return fail_hip(hipErrorUnknown, "nodes rebuild: label mirror");
+        max_pair = std::max(max_pair, nx ? c->h_xl[s_xl_off[i] + nx - 1] : s_label0[i]);
         m += 1 + nx;
         xw += nx;
         if (m >= 0xFFFFFFFFull) return ESC_E_LIMIT;
@@ -75,11 +106,11 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
     // the extra labels, compacted to the live nodes' words
     std::vector<uint32_t> h_xl((size_t)xw);
     for (int64_t i = 0; i < N; ++i) {
-        if ((nflags[i] & ESC_NF_ABSENT) || c->h_label0[i] == NONE) continue;
+        if ((nflags[i] & ESC_NF_ABSENT) || s_label0[i] == NONE) continue;
         const uint32_t nx = nf_xlbl(nflags[i]);
-        std::copy_n(c->h_xl.begin() + c->h_xl_off[i], nx, h_xl.begin() + xl_off[i]);
+        std::copy_n(c->h_xl.begin() + s_xl_off[i], nx, h_xl.begin() + xl_off[i]);
     }
-    const int64_t xl_cap = label_words((int64_t)xw, sf);
+    const int64_t xl_cap = std::max(label_words((int64_t)xw, sf), (int64_t)xw + S.min_free_xl);
     // group pairs: live entries sorted by node (start: where a pair's begin among the sorted
     // elements), then their spare ones; the entries of pairs no group selects follow all of
     // them as one run (pair NONE: nothing reads a piece of such a pair).  This rank's share
@@ -157,8 +188,8 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
 #endif
     // ---- list, sort, place
     RebuildDev R{};
-    R.flags = c->nodes.flags; R.label0 = c->nodes.label0; R.xl_off = c->nodes.d.xl_off; R.xl = c->nodes.d.xl;
-    R.cpu = c->nodes.cpu; R.mem = c->nodes.mem;
+    R.flags = S.flags; R.label0 = S.label0; R.xl_off = S.xl_off; R.xl = c->nodes.d.xl;
+    R.cpu = S.cpu; R.mem = S.mem;
     R.n_cap = NC; R.xl_len = c->xl_used;
     R.ne_off = view(P_NE); R.xl_off_new = view(P_XLO); R.trk_start = view(P_TRK); R.start = view(P_START);
     R.pair_lo = view(P_LO); R.piece_off = view(P_POFF); R.piece_pair = view(P_PPAIR);
@@ -184,12 +215,13 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
         const bool any = L.pair_next[q] > L.pair_lo[q];
         const uint32_t first = any ? h_e_node[L.pair_lo[q]] : NONE;      // sorted by node: the lowest
         if (any && (int64_t)first >= N) return fail_hip(hipErrorUnknown, "nodes rebuild: entry mirror");
-        gn[g] = group_node(L, q, first, any ? c->h_ncpu[first] : 0, any ? c->h_nmem[first] : 0);
+        gn[g] = group_node(L, q, first, any ? s_cpu[first] : 0, any ? s_mem[first] : 0);
     }
     if (G) HIP_TRY(hipMemcpy(b.gnode, gn.data(), gn.size() * sizeof(GroupNode), hipMemcpyHostToDevice));
     g_rebuild_ms[3] = (rebuild_clock() - t0) * 1e3;
     // ---- the swap: nothing below fails before the snapshot is whole again
     drop_graphs(c);                                          // captured steps hold the old buffers
+    if (S.commit) S.commit();                                // a compacted table becomes the resident one
     std::swap(c->nodes.d, B.nb);
     std::swap(c->d_ne_off, B.ne_off); std::swap(c->d_ne_pos, B.ne_pos);
     std::swap(c->d_nn_off, B.nn_off); std::swap(c->d_nn_list, B.nn_list);
@@ -227,6 +259,177 @@ int32_t nodes_rebuild_one(esc_ctx* c) {
     return rc;
 }
 
+// ------------------------------------------------------------------- compaction
+// The buffers a compaction builds beside the resident table; after the swap they hold the old
+// ones.  Released on every way out.
+struct CompactBufs {
+    uint32_t *flags = nullptr, *label0 = nullptr, *xl_off = nullptr, *nrun_off = nullptr, *nrun_len = nullptr;
+    int64_t *cpu = nullptr, *mem = nullptr, *created = nullptr, *inst = nullptr, *taint_s = nullptr;
+    uint8_t *no_delete = nullptr, *blob = nullptr;
+    int32_t* trk_node = nullptr;
+    PodRef* refs = nullptr;
+    ~CompactBufs() {
+        dfree(flags); dfree(label0); dfree(xl_off); dfree(nrun_off); dfree(nrun_len);
+        dfree(cpu); dfree(mem); dfree(created); dfree(inst); dfree(taint_s);
+        dfree(no_delete); dfree(blob); dfree(trk_node); dfree(refs);
+    }
+};
+thread_local double g_compact_ms[5];              // host plan, buffers + upload, gather + run move, host mirror remap,
+                                                  // and of the remap the O(pods) pass alone
+
+int32_t nodes_compact_one(esc_ctx* c, int64_t min_free_slots, int64_t min_free_xl_words, int64_t* new_index, int64_t cap) {
+    const int64_t N0 = c->n_nodes;
+    if (cap < N0) return ESC_E_LIMIT;
+    if (!c->d_inst || (int64_t)c->h_nflags.size() < N0 || (int64_t)c->h_label0.size() < N0 || (int64_t)c->h_created.size() != N0 ||
+        c->node_lo != 0 || c->node_hi != N0)
+        return ESC_E_STATE;
+    const bool facts = c->d_taint_s && c->d_no_delete;       // esc_load_placement's per-node facts exist
+    const bool runs = c->placed && c->d_refs && c->d_nrun_off && c->d_nrun_len;
+    if (runs && ((int64_t)c->h_run_off.size() < N0 + 1 || (int64_t)c->h_run_len.size() < N0)) return ESC_E_STATE;
+    hipSetDevice(c->device);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    double t0 = rebuild_clock();
+    for (double& x : g_compact_ms) x = 0;
+    // ---- the plan, from the host's mirrors alone
+    CompactPlan P;
+    if (const int32_t rc = plan_node_compact(P, c->h_nflags.data(), c->h_label0.data(), N0, c->spare_frac, min_free_slots,
+                                             min_free_xl_words, runs ? c->h_run_off.data() : nullptr,
+                                             runs ? c->h_run_len.data() : nullptr, runs ? c->h_run_pod.data() : nullptr))
+        return rc;
+    const int64_t L = P.n_live, NC = P.n_cap;
+    const int64_t refs_old = runs ? (int64_t)c->h_run_off.back() : 0;
+    const int64_t refs_new = runs ? (int64_t)P.run_off[NC] : 0;
+    std::vector<uint64_t> trk(c->h_trk);                     // monotone map: stays sorted
+    std::vector<int32_t> trk_node((size_t)std::max<int64_t>(c->trk_cap, 1), 0);
+    if ((int64_t)trk.size() > c->trk_cap) return ESC_E_STATE;
+    for (size_t k = 0; k < trk.size(); ++k) {
+        const uint64_t j = trk[k] >> 32;
+        if ((int64_t)j >= N0 || P.new_of[j] == NONE) return fail_hip(hipErrorUnknown, "nodes compact: tracker mirror");
+        trk[k] = ((uint64_t)P.new_of[j] << 32) | (uint32_t)trk[k];
+        trk_node[k] = (int32_t)P.new_of[j];
+    }
+    // ---- one staged copy of the plan's tables (the error word, zero, at its end)
+    static_assert(sizeof(RunMove) == 12, "k_run_move reads a move as three words");
+    struct Part { const void* p; size_t bytes, at; };
+    Part parts[] = {{P.src_of.data(), P.src_of.size() * 4, 0}, {P.moves.data(), P.moves.size() * sizeof(RunMove), 0},
+                    {P.run_off.data(), P.run_off.size() * 4, 0}, {P.run_len.data(), P.run_len.size() * 4, 0},
+                    {trk_node.data(), trk_node.size() * 4, 0}};
+    enum { C_SRC, C_MOVES, C_ROFF, C_RLEN, C_TRK };
+    size_t bytes = 0;
+    for (Part& q : parts) { q.at = bytes; bytes += (q.bytes + 255) & ~(size_t)255; }
+    const size_t err_at = bytes;
+    bytes += 256;
+    std::vector<uint8_t> stage(bytes, 0);
+    for (const Part& q : parts)
+        if (q.bytes) std::memcpy(stage.data() + q.at, q.p, q.bytes);
+    g_compact_ms[0] = (rebuild_clock() - t0) * 1e3;
+    t0 = rebuild_clock();
+    // ---- the new table, beside the resident one
+    CompactBufs B;
+    const size_t NCz = (size_t)std::max<int64_t>(NC, 1);
+    HIP_TRY(dalloc(&B.blob, bytes));
+    HIP_TRY(dalloc(&B.flags, NCz)); HIP_TRY(dalloc(&B.label0, NCz)); HIP_TRY(dalloc(&B.xl_off, NCz));
+    HIP_TRY(dalloc(&B.cpu, NCz)); HIP_TRY(dalloc(&B.mem, NCz)); HIP_TRY(dalloc(&B.created, NCz));
+    HIP_TRY(dalloc(&B.inst, NCz)); HIP_TRY(dalloc(&B.trk_node, trk_node.size()));
+    if (facts) { HIP_TRY(dalloc(&B.taint_s, NCz)); HIP_TRY(dalloc(&B.no_delete, NCz)); }
+    if (runs) {
+        HIP_TRY(dalloc(&B.refs, (size_t)std::max<int64_t>(refs_new, 1)));
+        HIP_TRY(dalloc(&B.nrun_off, (size_t)NC + 1)); HIP_TRY(dalloc(&B.nrun_len, NCz));
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(hipMemcpyAsync(B.blob, stage.data(), bytes, hipMemcpyHostToDevice, st));
+    auto view = [&](int k) { return reinterpret_cast<uint32_t*>(B.blob + parts[k].at); };
+    auto keep = [&](void* dst, int k) -> hipError_t {         // a table the snapshot keeps: its own buffer
+        return parts[k].bytes ? hipMemcpyAsync(dst, view(k), parts[k].bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    };
+    HIP_TRY(keep(B.trk_node, C_TRK));
+    if (runs) { HIP_TRY(keep(B.nrun_off, C_ROFF)); HIP_TRY(keep(B.nrun_len, C_RLEN)); }
+#if ESC_MEASURE
+    HIP_TRY(hipStreamSynchronize(st));                       // (the probe's split: the upload's end)
+    g_compact_ms[1] = (rebuild_clock() - t0) * 1e3;
+    t0 = rebuild_clock();
+#endif
+    // ---- gather the table, move the runs
+    CompactDev D{};
+    D.flags = c->nodes.flags; D.label0 = c->nodes.label0; D.xl_off = c->nodes.d.xl_off;
+    D.cpu = c->nodes.cpu; D.mem = c->nodes.mem; D.created = c->nodes.created; D.inst = c->d_inst;
+    D.taint_s = facts ? c->d_taint_s : nullptr; D.no_delete = facts ? c->d_no_delete : nullptr;
+    D.n_old = N0;
+    D.src_of = view(C_SRC); D.n_new = NC;
+    D.moves = view(C_MOVES); D.n_moves = runs ? (int64_t)P.moves.size() : 0;
+    D.flags_new = B.flags; D.label0_new = B.label0; D.xl_off_new = B.xl_off;
+    D.cpu_new = B.cpu; D.mem_new = B.mem; D.created_new = B.created; D.inst_new = B.inst;
+    D.taint_new = B.taint_s; D.nd_new = B.no_delete;
+    D.refs_old = reinterpret_cast<const uint32_t*>(c->d_refs); D.refs_new = reinterpret_cast<uint32_t*>(B.refs);
+    D.refs_old_words = refs_old * 5; D.refs_new_words = refs_new * 5;
+    D.err = reinterpret_cast<uint32_t*>(B.blob + err_at);
+    HIP_TRY(launch_nodes_compact(D, st));
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, D.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                       // the call's one wait before the rebuild's
+    if (err) return fail_fmt(ESC_E_HIP, "nodes compact: the node table does not fit the mirrors' plan (%u)", err);
+    g_compact_ms[2] = (rebuild_clock() - t0) * 1e3;
+    t0 = rebuild_clock();
+    // ---- the new table's mirrors, beside the resident ones (a mirror that disagrees with the
+    // table is reported, not repaired: they are permuted, never re-read)
+    std::vector<uint32_t> nflags(NCz, ESC_NF_ABSENT), label0(NCz, NONE), xl_off(NCz, 0);
+    std::vector<int64_t> ncpu(NCz, 0), nmem(NCz, 0), created((size_t)L);
+    for (int64_t i = 0; i < L; ++i) {
+        const uint32_t s = P.src_of[i];
+        nflags[i] = c->h_nflags[s]; label0[i] = c->h_label0[s]; xl_off[i] = c->h_xl_off[s];
+        ncpu[i] = c->h_ncpu[s]; nmem[i] = c->h_nmem[s]; created[i] = c->h_created[s];
+    }
+    std::vector<int32_t> run_pod;
+    if (runs) {
+        run_pod.assign((size_t)std::max<int64_t>(refs_new, 1), -1);
+        for (const RunMove& m : P.moves) std::copy_n(c->h_run_pod.begin() + m.src, m.len, run_pod.begin() + m.dst);
+    }
+    g_compact_ms[3] = (rebuild_clock() - t0) * 1e3;
+    // ---- the rebuild over the new table; its swap makes the table the resident one
+    bool swapped = false;
+    NodeSrc S;
+    S.flags = B.flags; S.label0 = B.label0; S.xl_off = B.xl_off; S.cpu = B.cpu; S.mem = B.mem;
+    S.n_nodes = L; S.n_cap = NC; S.min_free_xl = min_free_xl_words;
+    S.nflags = &nflags; S.hlabel0 = &label0; S.hxl_off = &xl_off; S.ncpu = &ncpu; S.nmem = &nmem; S.trk = &trk;
+    S.commit = [&]() {
+        const double t1 = rebuild_clock();
+        NodeBuf& b = c->nodes;
+        std::swap(b.flags, B.flags); std::swap(b.label0, B.label0); std::swap(b.cpu, B.cpu); std::swap(b.mem, B.mem);
+        std::swap(b.created, B.created); std::swap(b.trk_node, B.trk_node); std::swap(c->d_inst, B.inst);
+        if (facts) {
+            std::swap(c->d_taint_s, B.taint_s); std::swap(c->d_no_delete, B.no_delete);
+            c->rm_nodes = NC;
+        }
+        if (runs) {
+            // every bound pod follows its node's run; the pods of dead runs come out unbound
+            const double t2 = rebuild_clock();
+            const std::vector<uint32_t>& old_off = c->h_run_off;
+            par_chunks((int64_t)c->h_pod_node.size(), host_threads(), [&](int, int64_t lo, int64_t hi) {
+                for (int64_t i = lo; i < hi; ++i) {
+                    const uint32_t j = c->h_pod_node[i];
+                    if (j == NONE) continue;
+                    const uint32_t nj = (int64_t)j < N0 ? P.new_of[j] : NONE;
+                    c->h_pod_node[i] = nj;
+                    c->h_pod_rpos[i] = nj == NONE ? -1 : c->h_pod_rpos[i] - (int64_t)old_off[j] + (int64_t)P.run_off[nj];
+                }
+            });
+            g_compact_ms[4] = (rebuild_clock() - t2) * 1e3;
+            std::swap(c->d_refs, B.refs); std::swap(c->d_nrun_off, B.nrun_off); std::swap(c->d_nrun_len, B.nrun_len);
+            c->h_run_off.swap(P.run_off); c->h_run_len.swap(P.run_len); c->h_run_pod.swap(run_pod);
+        }
+        c->h_nflags.swap(nflags); c->h_label0.swap(label0); c->h_xl_off.swap(xl_off);
+        c->h_ncpu.swap(ncpu); c->h_nmem.swap(nmem); c->h_created.swap(created); c->h_trk.swap(trk);
+        c->n_nodes = L; c->n_cap = NC;
+        c->node_lo = 0; c->node_hi = L;
+        swapped = true;
+        g_compact_ms[3] += (rebuild_clock() - t1) * 1e3;
+    };
+    const int32_t rc = nodes_rebuild_from(c, S);
+    if (swapped)
+        for (int64_t j = 0; j < N0; ++j) new_index[j] = P.new_of[j] == NONE ? -1 : (int64_t)P.new_of[j];
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -236,7 +439,15 @@ int32_t esc_nodes_rebuild(esc_ctx* c) {
     if (!c) return ESC_E_INVAL;
     if (!c->has_device) return ESC_E_NODEV;
     if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
-    return nodes_rebuild_one(c);
+    return nodes_rebuild_from(c, resident_src(c));
+}
+
+int32_t esc_nodes_compact(esc_ctx* c, int64_t min_free_slots, int64_t min_free_xl_words, int64_t* new_index, int64_t cap) {
+    if (c && c->multi) return esc::multi_nodes_compact(c, min_free_slots, min_free_xl_words, new_index, cap);
+    if (!c || min_free_slots < 0 || min_free_xl_words < 0 || cap < 0 || (cap > 0 && !new_index)) return ESC_E_INVAL;
+    if (!c->has_device) return ESC_E_NODEV;
+    if (!c->nodes_loaded || c->stale) return ESC_E_STATE;
+    return nodes_compact_one(c, min_free_slots, min_free_xl_words, new_index, cap);
 }
 
 int32_t esc_nodes_room(const esc_ctx* c, int64_t* free_slots, int64_t* free_xl_words) {
@@ -256,6 +467,16 @@ int32_t esc_nodes_room(const esc_ctx* c, int64_t* free_slots, int64_t* free_xl_w
 int32_t esc_debug_rebuild_times(double* ms, int32_t n) {
     if (!ms || n < 0) return ESC_E_INVAL;
     for (int32_t k = 0; k < n && k < 6; ++k) ms[k] = g_rebuild_ms[k];
+    return ESC_OK;
+}
+
+// The last esc_nodes_compact of this thread before its rebuild part (ms): host plan, buffers and
+// upload, gather + run move to the wait, host mirror remap, the remap's O(pods) pass alone;
+// esc_debug_rebuild_times has the rest
+// (scripts/compact_probe.py).
+int32_t esc_debug_compact_times(double* ms, int32_t n) {
+    if (!ms || n < 0) return ESC_E_INVAL;
+    for (int32_t k = 0; k < n && k < 5; ++k) ms[k] = g_compact_ms[k];
     return ESC_OK;
 }
 #endif
@@ -469,6 +690,8 @@ int32_t esc_audit(esc_ctx* c, uint32_t checks, esc_audit_report* out) {
 //   4 occupancy word `index` of [2][n_entries] = value       5 touch bitmap: workgroup `index`, set column `value` cleared
 //   6 node `index`: ESC_NF_TRACKED flipped in the device node table only
 //   7 group `index`: GroupNode::first_cpu = value            8 node `index`: the host mirror h_ncpu = value
+//   9 deleted slot `index`: ESC_NF_ABSENT cleared in the host mirror h_nflags only (esc_nodes_compact
+//     then plans a source the table calls absent; k_node_gather reports it)
 // Everything else is ESC_E_INVAL.
 int32_t esc_debug_poke(esc_ctx* c, int32_t what, int64_t index, int64_t value) {
     if (!c || c->multi || index < 0) return ESC_E_INVAL;
@@ -540,6 +763,10 @@ int32_t esc_debug_poke(esc_ctx* c, int32_t what, int64_t index, int64_t value) {
     case 8:
         if (index >= c->n_nodes || (c->h_nflags[index] & ESC_NF_ABSENT)) return ESC_E_INVAL;
         c->h_ncpu[index] = value;
+        return ESC_OK;
+    case 9:
+        if (index >= c->n_nodes || !(c->h_nflags[index] & ESC_NF_ABSENT)) return ESC_E_INVAL;
+        c->h_nflags[index] &= ~ESC_NF_ABSENT;
         return ESC_OK;
     default:
         return ESC_E_INVAL;

@@ -210,29 +210,6 @@ void put_kb(uint32_t* kb, int width, int64_t at, uint64_t v) {
     else reinterpret_cast<uint16_t*>(kb)[at] = (uint16_t)v;
 }
 
-// Host threads for the load-time layout passes: ESC_HOST_THREADS, else OMP_NUM_THREADS (the
-// GPU box sets 16, its CPU share per GPU), else min(16, hardware threads).
-int host_threads() {
-    int n = 0;
-    for (const char* e : {"ESC_HOST_THREADS", "OMP_NUM_THREADS"})
-        if (const char* v = std::getenv(e)) { n = std::atoi(v); if (n > 0) break; }
-    if (n <= 0) n = std::min<int>(16, std::max(1u, std::thread::hardware_concurrency()));
-    return std::max(1, std::min(n, 64));
-}
-
-// f(t, lo, hi) over T contiguous chunks of [0, n), one host thread each (in order for T = 1)
-template <class F>
-void par_chunks(int64_t n, int T, F&& f) {
-    if (T <= 1 || n < 4096) {
-        f(0, (int64_t)0, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    th.reserve(T);
-    for (int t = 0; t < T; ++t) th.emplace_back([&, t] { f(t, n * t / T, n * (t + 1) / T); });
-    for (auto& x : th) x.join();
-}
-
 // Spare C slots (esc_load_pods with esc_set_spare): room per slot, slots per 64-pod tile.
 constexpr int CS_SLOTS = 16, CS_XREG = 4, CS_XINIT = 2, CS_REC = CS_XREG + CS_XINIT + 1, CS_XP = 6;
 static_assert(CS_SLOTS * CS_REC <= 128 && CS_SLOTS * CS_XP <= 128, "a spare C tile stays on K1's C path");
@@ -4073,18 +4050,9 @@ int32_t esc_load_placement(esc_ctx* c, const uint32_t* pod_node, const int64_t* 
         for (int64_t i = 0; i < np; ++i)
             if (c->pod_cls[i] != -2 && pod_node[i] != NONE) { ++cnt[pod_node[i]]; ++bound; }
         for (int64_t j = 0; j < N; ++j) live += (c->h_nflags[j] & ESC_NF_ABSENT) ? 0 : 1;
-        // room for pods bound later: a node's own count with the spare fraction on top, and at
-        // least the mean pods per node with the spare fraction on top — what a lightly loaded
-        // node, or a table slot with no node yet (added later), gets; the scheduler fills those
-        const uint64_t cap_new = c->spare_frac > 0
-            ? (uint64_t)std::ceil((double)bound / (double)std::max<int64_t>(live, 1) * (1.0 + c->spare_frac)) + 4 : 0;
-        std::vector<uint32_t> off(NC + 1, 0);
-        for (int64_t j = 0; j < NC; ++j) {
-            const uint64_t own = cnt[j] + (c->spare_frac > 0 ? (uint64_t)std::ceil(cnt[j] * c->spare_frac) + 2 : 0);
-            const uint64_t cap = j >= N ? cap_new : std::max(own, cap_new);
-            if ((uint64_t)off[j] + cap >= 0xFFFFFFFFull) return ESC_E_LIMIT;
-            off[j + 1] = off[j] + (uint32_t)cap;
-        }
+        // room for pods bound later: plan_runs' rule (esc_node_layout.h), shared with esc_nodes_compact
+        std::vector<uint32_t> off;
+        if (const int32_t rc = plan_runs(off, cnt.data(), NC, N, bound, live, c->spare_frac)) return rc;
         const int64_t total = off[NC];
         std::vector<uint32_t> len(std::max<int64_t>(NC, 1), 0), slot(std::max<int64_t>(total, 1), 0);
         c->h_run_pod.assign(std::max<int64_t>(total, 1), -1);

@@ -7,7 +7,10 @@ snapshot indices, and this queue is what maps a pod key or a node name to one, h
 recycles pod ids, batches a scan's events into at most one call per kind and falls back to
 one full reload when ``ESC_E_LIMIT`` says the spare room ran out.  With ``rebuild=True`` a
 node call that answers ``ESC_E_LIMIT`` is first answered by ``nodes_rebuild`` (the node side
-re-derived on the device, no pod reloaded) and retried once.
+re-derived on the device, no pod reloaded) and retried once.  With ``compact=True`` a
+``nodes_add`` that lacks free table slots, and a ``pods_bind`` into a full run, are answered by
+``nodes_compact`` (the live nodes renumbered into a fresh table on the device, the runs re-cut)
+and retried once; the queue's index maps follow the returned map.
 
 It holds the current objects (plain-dict records, escalator_amd/objects.py) — the truth a
 reload is built from — and, beside them, what the device last saw of each.  Ingest
@@ -67,11 +70,14 @@ def _status(n: dict):
 
 
 class EventQueue:
-    def __init__(self, spare: float = 0.5, rebuild: bool = False):
+    def __init__(self, spare: float = 0.5, rebuild: bool = False, compact: bool = False):
         self.spare = float(spare)
-        self.rebuild = bool(rebuild)               # answer a node-side ESC_E_LIMIT with nodes_rebuild first
+        self.compact = bool(compact)               # answer a lack of table slots / a full run with nodes_compact
+        self.rebuild = bool(rebuild) or self.compact   # answer a node-side ESC_E_LIMIT with nodes_rebuild first
         self.rebuilds = 0
         self.rebuild_causes: list[str] = []        # the call that answered ESC_E_LIMIT, or "audit:<check>"
+        self.compactions = 0
+        self.compact_causes: list[str] = []        # the call that answered ESC_E_LIMIT
         self.pods: dict[str, dict] = {}            # the object store: key -> pod, name -> node
         self.nodes: dict[str, dict] = {}           # (insertion order = arrival order)
         self._dev_pods: dict[str, dict] = {}       # the records the device holds, as last flushed
@@ -171,16 +177,24 @@ class EventQueue:
         self.applied[kind] += n
         return rc
 
-    def _node_call(self, ctx, kind: str, n: int, slots: int, fn, *args):
+    def _node_call(self, ctx, kind: str, n: int, slots: int, xl_words: int, fn, *args):
         """A nodes_add / nodes_relabel call: with ``rebuild`` on, its first ESC_E_LIMIT is
         answered by one node-side rebuild (when the table has the `slots` free slots the call
-        needs: a rebuild does not grow the table) and one retry; the second reloads."""
+        needs: a rebuild does not grow the table) and one retry; the second reloads.  With
+        ``compact`` on, too few free slots are answered by one compaction (which includes the
+        rebuild) with room for the batch's `slots` and `xl_words`, and one retry."""
         try:
             return self._call(kind, n, fn, *args)
         except _Reload:
-            if not self.rebuild or (slots and ctx.nodes_room()[0] < slots):
+            if not self.rebuild:
                 raise
-        self.node_rebuild(ctx, kind)
+            short = bool(slots) and ctx.nodes_room()[0] < slots
+            if short and not self.compact:
+                raise
+        if short:
+            self.node_compact(ctx, kind, slots, xl_words)
+        else:
+            self.node_rebuild(ctx, kind)
         return self._call(kind, n, fn, *args)
 
     def node_rebuild(self, ctx, cause: str):
@@ -189,6 +203,21 @@ class EventQueue:
         ctx.nodes_rebuild()
         self.rebuilds += 1
         self.rebuild_causes.append(cause)
+
+    def node_compact(self, ctx, cause: str, slots: int = 0, xl_words: int = 0):
+        """One ``nodes_compact``: `cause` goes into ``compact_causes`` and the index maps follow
+        the returned map (in place: a flush in progress holds them).  Pods, the trackers and
+        the instantiation times stay as they are."""
+        new = ctx.nodes_compact(min_free_slots=slots, min_free_xl_words=xl_words)
+        moved = {m: int(new[j]) for m, j in self._node_idx.items()}
+        assert all(j >= 0 for j in moved.values()), "a node the queue holds was absent on the device"
+        self._node_idx.clear()
+        self._node_idx.update(moved)
+        self._idx_node.clear()
+        self._idx_node.update((j, m) for m, j in moved.items())
+        self.compactions += 1
+        self.compact_causes.append(cause)
+        self.touched_nodes = True
 
     def _target(self, pod: dict) -> int:
         return self._node_idx.get(pod.get("node_name") or "", NONE) if pod.get("node_name") else NONE
@@ -232,7 +261,8 @@ class EventQueue:
         new = [m for m in self.nodes if m in dirty_n and m not in dev_n]
         if new:
             _, packed = ctx.pack([], [self.nodes[m] for m in new])
-            ids = self._node_call(ctx, "nodes_add", len(new), len(new), ctx.nodes_add, packed)
+            ids = self._node_call(ctx, "nodes_add", len(new), len(new), len(packed.get("xl_pair", ())), ctx.nodes_add,
+                                  packed)
             for m, j in zip(new, ids):
                 idx[m] = int(j)
                 self._idx_node[int(j)] = m
@@ -252,7 +282,7 @@ class EventQueue:
                 facts.append(m)
         if relabel:
             _, packed = ctx.pack([], [self.nodes[m] for m in relabel])
-            self._node_call(ctx, "nodes_relabel", len(relabel), 0, ctx.nodes_relabel,
+            self._node_call(ctx, "nodes_relabel", len(relabel), 0, 0, ctx.nodes_relabel,
                             np.array([idx[m] for m in relabel], np.int64), packed)
         if update:
             _, packed = ctx.pack([], [self.nodes[m] for m in update])
@@ -297,8 +327,17 @@ class EventQueue:
             if k in self.pods:
                 dev_p[k] = self.pods[k]
         if bind:
-            self._call("pods_bind", len(bind), ctx.pods_bind, np.array([pid[k] for k in bind], np.int64),
-                       np.array([self._target(self.pods[k]) for k in bind], np.uint32))
+            ids = np.array([pid[k] for k in bind], np.int64)
+            try:
+                self._call("pods_bind", len(bind), ctx.pods_bind, ids,
+                           np.array([self._target(self.pods[k]) for k in bind], np.uint32))
+            except _Reload:
+                if not self.compact:
+                    raise
+                # a full run: the compaction re-cuts the runs (the targets' indices change with it)
+                self.node_compact(ctx, "pods_bind")
+                self._call("pods_bind", len(bind), ctx.pods_bind, ids,
+                           np.array([self._target(self.pods[k]) for k in bind], np.uint32))
 
     def _reload(self, ctx, dirty_p, dirty_n):
         """One full load from the object store: the nodes the device held keep their order

@@ -764,8 +764,28 @@ func (x *Context) NodesRebuild() error {
 	return rcErr("esc_nodes_rebuild", C.esc_nodes_rebuild(x.c))
 }
 
+// NodesCompact renumbers the live nodes densely on the device into a table with fresh free
+// slots and extra-label room (at least minFreeSlots and minFreeXLWords), re-cuts the
+// placement's runs and derives the node side as NodesRebuild does (esc_nodes_compact); no
+// pod is reloaded.  It returns the new index of every old slot, -1 for a deleted one: the
+// caller's name -> index maps follow it.  The answer to NodesAdd's ErrReload when NodesRoom
+// shows too few slots, and to PodsBind's ErrReload (a full run).
+func (x *Context) NodesCompact(minFreeSlots, minFreeXLWords int64) ([]int64, error) {
+	var pods, nodes C.int64_t
+	if err := rcErr("esc_ctx_counts", C.esc_ctx_counts(x.c, &pods, &nodes)); err != nil {
+		return nil, err
+	}
+	newIndex := make([]int64, int(nodes))
+	err := rcErr("esc_nodes_compact", C.esc_nodes_compact(x.c, C.int64_t(minFreeSlots), C.int64_t(minFreeXLWords),
+		(*C.int64_t)(unsafe.Pointer(ptr(newIndex))), C.int64_t(len(newIndex))))
+	if err != nil {
+		return nil, err
+	}
+	return newIndex, nil
+}
+
 // NodesRoom returns the free node-table slots and extra-label words (esc_nodes_room): a
-// rebuild does not grow the table, so more adds than free slots still need a Load.
+// rebuild does not grow the table, so more adds than free slots need NodesCompact.
 func (x *Context) NodesRoom() (freeSlots, freeXLWords int64, err error) {
 	var a, b C.int64_t
 	err = rcErr("esc_nodes_room", C.esc_nodes_room(x.c, &a, &b))

@@ -556,9 +556,33 @@ int32_t esc_nodes_relabel(esc_ctx* ctx, const int64_t* ids, const esc_node_soa* 
  * the table is reported (ESC_E_HIP), not repaired.  ESC_E_NODEV without a device,
  * ESC_E_STATE without a node table or on a stale context.  A rebuild does not grow the
  * table: esc_nodes_room tells the free table slots and extra-label words (either may be
- * null); an add that needs more slots than are free still needs esc_load_nodes. */
+ * null); an add that needs more slots than are free needs esc_nodes_compact. */
 int32_t esc_nodes_rebuild(esc_ctx* ctx);
 int32_t esc_nodes_room(const esc_ctx* ctx, int64_t* free_slots, int64_t* free_xl_words);
+/* Turnover uses the table's slots up (a deleted slot is not reused) and a node's run of
+ * PodRefs can fill: esc_nodes_compact renumbers the live nodes densely on the device, in
+ * ascending old index (so the lister order, the tie order and allNodes[0] stay), into a table
+ * with n_cap = max(table_slots(L, f), L + min_free_slots) slots and extra-label room for
+ * max(label_words(w, f), w + min_free_xl_words) words (L live nodes carrying w extra-label
+ * words, f the esc_set_spare fraction), re-cuts the placement's runs with esc_load_placement's
+ * capacity rule applied to the current lengths, then derives the node side as
+ * esc_nodes_rebuild does.  No pod block is read or written.  After it the node numbering is
+ * that of a fresh load of the live nodes in snapshot order.
+ * new_index[old] receives the new index of every old slot < the old node count, -1 for an
+ * absent one; cap is the array's length (cap below the old node count: ESC_E_LIMIT, nothing
+ * changed; NULL with cap 0 is allowed).
+ * Renumbered: the node table's columns, the extra labels, instantiation times, taint times,
+ * no-delete bytes, the tracker list's node ids, every PodRef run (in its order); the pods of
+ * deleted nodes' runs come out unbound.  Kept: pod blocks, replicas and ids, the K1 plan /
+ * calibration / touch tables, esc_set_state, group ownership, the tracker's membership.
+ * Derived afresh and invalidated: as esc_nodes_rebuild.  All or nothing up to the swap, as
+ * there: ESC_E_HIP when the table disagrees with the mirrors' plan, nothing changed.
+ * ESC_E_INVAL for a NULL context or a negative minimum, ESC_E_LIMIT for a table of 2^28
+ * slots or more or PodRefs past 32-bit offsets, ESC_E_NODEV, ESC_E_STATE as above.
+ * Ranks of a sharded job each make the call with the same arguments (no collective).
+ * esc_nodes_room then reports n_cap - L. */
+int32_t esc_nodes_compact(esc_ctx* ctx, int64_t min_free_slots, int64_t min_free_xl_words,
+                          int64_t* new_index, int64_t cap);
 
 /* ------------------------------------------- dry-mode taintTracker (§8f rank 4)
  * nodeGroup.taintTracker (controller.go:35) as interned (node, group) pairs on the
