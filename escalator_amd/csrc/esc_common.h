@@ -218,6 +218,27 @@ ESC_HD bool pf_default_ok(uint32_t f) {
 }
 ESC_HD uint32_t nf_xlbl(uint32_t f) { return (f >> ESC_NF_XLBL_SHIFT) & ESC_PF_CNT_MASK; }
 
+// Effective request of one pod — ComputePodResourceRequest, scheduler/types.go:72-89:
+// regular containers summed (Resource.Add, plain int64 += wraps), then max with every
+// init container (SetMaxResource; an absent key is INT64_MIN so max() ignores it),
+// then the overhead record added.  `o` walks the pod's extra records.  The one definition:
+// the kernels that read records from memory call it, and so does the host when it folds a
+// packed pod's records into one request at load (esc_kernels.h, kp_fold).
+ESC_HD void pod_request(uint32_t f, uint32_t cpu0, int64_t mem0, const int64_t* xc_cpu, const int64_t* xc_mem,
+                        uint32_t& o, int64_t& cpu, int64_t& mem) {
+    uint64_t c = cpu0, m = (uint64_t)mem0;
+    const uint32_t nreg = pf_xreg(f), ninit = pf_xinit(f);
+    for (uint32_t r = 0; r < nreg; ++r, ++o) { c += (uint64_t)xc_cpu[o]; m += (uint64_t)xc_mem[o]; }
+    for (uint32_t r = 0; r < ninit; ++r, ++o) {
+        const int64_t ic = xc_cpu[o], im = xc_mem[o];
+        c = ((int64_t)c >= ic) ? c : (uint64_t)ic;
+        m = ((int64_t)m >= im) ? m : (uint64_t)im;
+    }
+    if (f & ESC_PF_HAS_OVH) { c += (uint64_t)xc_cpu[o]; m += (uint64_t)xc_mem[o]; ++o; }
+    cpu = (int64_t)c;
+    mem = (int64_t)m;
+}
+
 // ------------------------------------------------- node-side layout constants
 // What K2 and the host's layout plan (esc_node_layout.h) share: a piece is a run of entries
 // of one pair, a span the whole pieces one K2 wave reduces.

@@ -298,7 +298,7 @@ struct esc_ctx {
     std::vector<uint32_t> h_cused;                            // a C slot's pod's own records | pairs << 16
     std::vector<uint32_t> h_xc_base, h_xp_base;               // C tiles' record / pair offsets
     int64_t live_pods = 0, live_xc = 0, live_xp = 0;
-    int64_t live_pk_pods = 0, live_pk_xc = 0;   // of them in packed K classes (either size)
+    int64_t live_pk_pods = 0;                   // of them in packed K classes (either size; no records there)
     int64_t live_p8_pods = 0, live_p8_xp = 0;   // of them in packed small K classes, their extra pairs
     int64_t c_tiles_loaded = 0;                 // C tiles of loaded pods (the spare C tiles excluded)
     // node state mirrors for esc_nodes_update

@@ -104,26 +104,7 @@ __device__ __forceinline__ void g_add(int64_t* a, int64_t v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(a), (unsigned long long)v);
 }
 
-// Effective request of one pod — ComputePodResourceRequest, scheduler/types.go:72-89:
-// regular containers summed (Resource.Add, plain int64 += wraps), then max with every
-// init container (SetMaxResource; an absent key is INT64_MIN so max() ignores it),
-// then the overhead record added.  `o` walks the pod's extra records.
-__device__ __forceinline__ void pod_request(uint32_t f, uint32_t cpu0, int64_t mem0,
-                                            const int64_t* __restrict__ xc_cpu,
-                                            const int64_t* __restrict__ xc_mem, uint32_t& o,
-                                            int64_t& cpu, int64_t& mem) {
-    uint64_t c = cpu0, m = (uint64_t)mem0;
-    const uint32_t nreg = pf_xreg(f), ninit = pf_xinit(f);
-    for (uint32_t r = 0; r < nreg; ++r, ++o) { c += (uint64_t)xc_cpu[o]; m += (uint64_t)xc_mem[o]; }
-    for (uint32_t r = 0; r < ninit; ++r, ++o) {
-        const int64_t ic = xc_cpu[o], im = xc_mem[o];
-        c = ((int64_t)c >= ic) ? c : (uint64_t)ic;
-        m = ((int64_t)m >= im) ? m : (uint64_t)im;
-    }
-    if (f & ESC_PF_HAS_OVH) { c += (uint64_t)xc_cpu[o]; m += (uint64_t)xc_mem[o]; ++o; }
-    cpu = (int64_t)c;
-    mem = (int64_t)m;
-}
+// (pod_request, the effective request of one pod from its records: esc_common.h)
 
 // ------------------------------------------------------------- wave primitives
 // DPP lane movement (no LDS traffic).  Out-of-row sources and masked rows read 0.
@@ -276,17 +257,16 @@ struct KTile<R, NXP, 0> {            // plain block
     ulonglong2 rc[R > 0 ? R : 1][2], rm[R > 0 ? R : 1][2];
     uint4 rq[NXP > 0 ? NXP : 1];
 };
-template <int R, int NXP>
-struct KTile<R, NXP, 2> {            // packed small block (esc_kernels.h, kp8_*)
-    ulonglong2 w[2];                 // cpu0 | mem0 << 14 | pair0 << 48 | flags << 62
-    ulonglong2 r[R > 0 ? R : 1][2];  // records, cpu | mem << 20
+// (packed blocks hold no records: the host folded them into the pod's request, kp_fold)
+template <int NXP>
+struct KTile<0, NXP, 2> {            // packed small block (esc_kernels.h, kp8_*)
+    ulonglong2 w[2];                 // cpu | mem << 14 | pair0 << 48 | flags << 62
     uint2 rq[NXP > 0 ? NXP : 1];     // u16 pairs, 4 per lane
 };
-template <int R, int NXP>
-struct KTile<R, NXP, 1> {            // packed block (esc_kernels.h, kp_*)
+template <int NXP>
+struct KTile<0, NXP, 1> {            // packed block (esc_kernels.h, kp_*)
     uint4 a;                         // pair0 | pod flags << 28
-    ulonglong2 cm[2];                // cpu0 | mem0 << 20
-    ulonglong2 r[R > 0 ? R : 1][2];  // records, cpu | mem << 20
+    ulonglong2 cm[2];                // cpu | mem << 20
     uint4 rq[NXP > 0 ? NXP : 1];
 };
 
@@ -319,40 +299,27 @@ __device__ __forceinline__ PodClass load_class(const PodClass* cls, int i) {
 // One tile = one contiguous block (esc_kernels.h, K blocks): every load below is lane l's
 // 16 B at a compile-time offset from the block's first word, through the run's descriptor
 // (`to` = the tile's byte offset in the run; RUN_OOB past its end: zeros, no traffic).
-template <int R, int NXP>
-__device__ __forceinline__ void k_load(Rsrc rs, uint32_t to, uint32_t lane, KTile<R, NXP, 2>& T, const PodClass&) {
+template <int NXP>
+__device__ __forceinline__ void k_load(Rsrc rs, uint32_t to, uint32_t lane, KTile<0, NXP, 2>& T, const PodClass&) {
     const uint32_t o = to + lane * 16;
-    auto w = [&](int words) { return o + 4u * (uint32_t)words; };
     T.w[0] = ldb2(rs, o);
-    T.w[1] = ldb2(rs, w(256));
+    T.w[1] = ldb2(rs, o + 4u * 256u);
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-        T.r[k][0] = ldb2(rs, w(KP8_REC + 512 * k));
-        T.r[k][1] = ldb2(rs, w(KP8_REC + 512 * k + 256));
-    }
-#pragma unroll
-    for (int k = 0; k < NXP; ++k) T.rq[k] = ldb8(rs, to + lane * 8 + 4u * (KP8_REC + 512 * R + 128 * k));
+    for (int k = 0; k < NXP; ++k) T.rq[k] = ldb8(rs, to + lane * 8 + 4u * (KP8_XP + 128 * k));
 }
 
 // Packed (12-B) blocks: since the small blocks take most pods, one pipeline for every
-// shape (R = NXP = 3 at most, the class's counts select the rows, as for plain blocks).
-template <int R, int NXP>
-__device__ __forceinline__ void k_load(Rsrc rs, uint32_t to, uint32_t lane, KTile<R, NXP, 1>& T, const PodClass& C) {
+// shape (NXP = 3 at most, the class's count selects the rows, as for plain blocks).
+template <int NXP>
+__device__ __forceinline__ void k_load(Rsrc rs, uint32_t to, uint32_t lane, KTile<0, NXP, 1>& T, const PodClass& C) {
     const uint32_t o = to + lane * 16;
-    const uint32_t nr = kb_nrec(C);
     auto w = [&](int words) { return o + 4u * (uint32_t)words; };
     T.a = ldb4(rs, o);
     T.cm[0] = ldb2(rs, w(KP_CM0));
     T.cm[1] = ldb2(rs, w(KP_CM0 + 256));
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const bool on = (uint32_t)k < nr;
-        T.r[k][0] = ldb2(rs, on ? w(KP_REC + 512 * k) : RUN_OOB);
-        T.r[k][1] = ldb2(rs, on ? w(KP_REC + 512 * k + 256) : RUN_OOB);
-    }
-#pragma unroll
     for (int k = 0; k < NXP; ++k)
-        T.rq[k] = ldb4(rs, (uint32_t)k < C.nxp ? o + 4u * (KP_REC + 512u * nr + 256u * (uint32_t)k) : RUN_OOB);
+        T.rq[k] = ldb4(rs, (uint32_t)k < C.nxp ? o + 4u * (KP_XP + 256u * (uint32_t)k) : RUN_OOB);
 }
 
 // Plain blocks (pods outside the packed ranges: rare) go through ONE pipeline for every
@@ -381,104 +348,66 @@ __device__ __forceinline__ void k_load(Rsrc rs, uint32_t to, uint32_t lane, KTil
         T.rq[k] = ldb4(rs, (uint32_t)k < C.nxp ? o + 4u * (KB_REC + 1024u * nr + 256u * (uint32_t)k) : RUN_OOB);
 }
 
-// ComputePodResourceRequest (scheduler/types.go:72-89) for each of the lane's 4 pods:
-// records [0, xreg) are regular containers (add), [xreg, xreg + xinit) init containers
-// (max; an absent key is INT64_MIN), the last the overhead (add), with Go's wrapping
-// int64 +=; then the pod's memberships (node_group.go:218-275).
-// The same for a packed block: values unpacked in registers (an init record's absent key
-// — its field's sentinel — takes no part in the max, as INT64_MIN would not).
+// A packed block's pods: the stored request is the pod's effective one (folded on the host,
+// kp_fold) and inside the LDS range by construction, so each pod is only its memberships
+// (node_group.go:218-275).
 template <int R, int NXP, int ABLATE>
 __device__ __forceinline__ void k_process(const GroupDev& G, const PodSink<ABLATE>& K, const PodClass& C,
                                           const KTile<R, NXP, 1>& T) {
-    const uint32_t init_end = C.xreg + C.xinit;
 #pragma unroll
     for (int j = 0; j < PODS_PER_LANE; ++j) {
         const uint32_t a = lane4(T.a, j);
         if (a & (ESC_PF_DAEMONSET << KP_FLAG_SHIFT)) continue;      // node_group.go:221, :259
         const uint64_t cm = lane4(T.cm, j);
-        uint64_t cpu = cm & KP_CPU_ABSENT, mem = cm >> KP_CPU_BITS;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const uint64_t v = lane4(T.r[k], j);
-            const uint64_t c = v & KP_CPU_ABSENT, m = v >> KP_CPU_BITS;
-            if ((uint32_t)k < C.xreg || (uint32_t)k >= init_end) {
-                cpu += c;
-                mem += m;
-            } else {                                   // values and sums are >= 0 here
-                cpu = (c == KP_CPU_ABSENT || cpu >= c) ? cpu : c;
-                mem = (m == KP_MEM_ABSENT || mem >= m) ? mem : m;
-            }
-        }
-        const bool in = in_range(cpu, mem);
-        if ((a >> KP_FLAG_SHIFT) == 0 && G.default_group != NONE) K.add(G.n_gp, cpu, mem, in);   // pf_default_ok
+        const uint64_t cpu = cm & KP_CPU_ABSENT, mem = cm >> KP_CPU_BITS;
+        if ((a >> KP_FLAG_SHIFT) == 0 && G.default_group != NONE) K.add(G.n_gp, cpu, mem, true);   // pf_default_ok
         const uint32_t q0 = a & KP_PAIR_NONE;
-        if (q0 < G.n_gp) K.add(q0, cpu, mem, in);
+        if (q0 < G.n_gp) K.add(q0, cpu, mem, true);
 #pragma unroll
         for (int k = 0; k < NXP; ++k) {
             const uint32_t q = lane4(T.rq[k], j);
-            if ((uint32_t)k < C.nxp && q < G.n_gp) K.add(q, cpu, mem, in);   // rows past the class's: zeros
+            if ((uint32_t)k < C.nxp && q < G.n_gp) K.add(q, cpu, mem, true);   // rows past the class's: zeros
         }
     }
 }
 
-// The packed small block: one u64 per pod (kp8_*), records as in the packed block.
+// The packed small block: one u64 per pod (kp8_*).
 template <int R, int NXP, int ABLATE>
-__device__ __forceinline__ void k_process(const GroupDev& G, const PodSink<ABLATE>& K, const PodClass& C,
+__device__ __forceinline__ void k_process(const GroupDev&, const PodSink<ABLATE>& K, const PodClass&,
                                           const KTile<R, NXP, 2>& T) {
-    const uint32_t init_end = C.xreg + C.xinit;
 #pragma unroll
     for (int j = 0; j < PODS_PER_LANE; ++j) {
         // (a daemonset pod, node_group.go:221 / :259, is stored with no pairs and
         // blocks-default set: it is added nowhere, no test needed)
         const uint64_t w = lane4(T.w, j);
-        uint64_t cpu = w & KP8_CPU_MASK, mem = (w >> KP8_CPU_BITS) & KP8_MEM_MASK;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const uint64_t v = lane4(T.r[k], j);
-            const uint64_t c = v & KP_CPU_ABSENT, m = v >> KP_CPU_BITS;
-            if ((uint32_t)k < C.xreg || (uint32_t)k >= init_end) {
-                cpu += c;
-                mem += m;
-            } else {                                   // values and sums are >= 0 here
-                cpu = (c == KP_CPU_ABSENT || cpu >= c) ? cpu : c;
-                mem = (m == KP_MEM_ABSENT || mem >= m) ? mem : m;
-            }
-        }
-        // without records the pod is inside the LDS range by construction (2^14, 2^34)
-        const bool in = R == 0 ? true : in_range(cpu, mem);
+        const uint64_t cpu = w & KP8_CPU_MASK, mem = (w >> KP8_CPU_BITS) & KP8_MEM_MASK;
         const uint32_t q0 = (uint32_t)(w >> KP8_PAIR_SHIFT) & KP8_PAIR_NONE;
-        if (in) {
-            if constexpr (ABLATE & 1) {
-                asm volatile("" :: "v"(q0), "v"(cpu), "v"(mem));
-            } else {
-                // slot adds straight to LDS: pair q is slot q - g0 of this window when below
-                // plim (NONE and pairs no group selects are above it), the default slot
-                // when the pod passes the default filter (pf_default_ok)
-                const uint64_t vcc = cpu | (1ull << CNT_SHIFT);
-                if (K.acc.dslot != NONE && !(w & KP8_NODEF)) {
-                    lds_add(K.acc.cc + K.acc.dslot, vcc);
-                    lds_add(K.acc.mem + K.acc.dslot, mem);
-                }
-                const uint32_t i0 = q0 - (uint32_t)K.acc.g0;
-                if (i0 < K.acc.plim) { lds_add(K.acc.cc + i0, vcc); lds_add(K.acc.mem + i0, mem); }
-#pragma unroll
-                for (int k = 0; k < NXP; ++k) {
-                    const uint32_t i = kp8_xp(T.rq[k], j) - (uint32_t)K.acc.g0;
-                    if (i < K.acc.plim) { lds_add(K.acc.cc + i, vcc); lds_add(K.acc.mem + i, mem); }
-                }
+        if constexpr (ABLATE & 1) {
+            asm volatile("" :: "v"(q0), "v"(cpu), "v"(mem));
+        } else {
+            // slot adds straight to LDS: pair q is slot q - g0 of this window when below
+            // plim (NONE and pairs no group selects are above it), the default slot
+            // when the pod passes the default filter (pf_default_ok)
+            const uint64_t vcc = cpu | (1ull << CNT_SHIFT);
+            if (K.acc.dslot != NONE && !(w & KP8_NODEF)) {
+                lds_add(K.acc.cc + K.acc.dslot, vcc);
+                lds_add(K.acc.mem + K.acc.dslot, mem);
             }
-        } else {                                       // outside the LDS range: the exact words
-            if (!(w & KP8_NODEF) && G.default_group != NONE) K.add(G.n_gp, cpu, mem, false);
-            if (q0 < G.n_gp) K.add(q0, cpu, mem, false);
+            const uint32_t i0 = q0 - (uint32_t)K.acc.g0;
+            if (i0 < K.acc.plim) { lds_add(K.acc.cc + i0, vcc); lds_add(K.acc.mem + i0, mem); }
 #pragma unroll
             for (int k = 0; k < NXP; ++k) {
-                const uint32_t q = kp8_xp(T.rq[k], j);
-                if (q < G.n_gp) K.add(q, cpu, mem, false);
+                const uint32_t i = kp8_xp(T.rq[k], j) - (uint32_t)K.acc.g0;
+                if (i < K.acc.plim) { lds_add(K.acc.cc + i, vcc); lds_add(K.acc.mem + i, mem); }
             }
         }
     }
 }
 
+// ComputePodResourceRequest (scheduler/types.go:72-89) for each of the lane's 4 pods of a
+// plain block: records [0, xreg) are regular containers (add), [xreg, xreg + xinit) init
+// containers (max; an absent key is INT64_MIN), the last the overhead (add), with Go's
+// wrapping int64 +=; then the pod's memberships (node_group.go:218-275).
 template <int R, int NXP, int ABLATE>
 __device__ __forceinline__ void k_process(const GroupDev& G, const PodSink<ABLATE>& K, const PodClass& C,
                                           const KTile<R, NXP, 0>& T) {
@@ -516,10 +445,6 @@ __device__ __forceinline__ void k_sink(const KTile<R, NXP, 2>& T) {   // loads-o
     uint64_t y = T.w[0].x ^ T.w[0].y ^ T.w[1].x ^ T.w[1].y;
     uint32_t x = 0;
 #pragma unroll
-    for (int k = 0; k < R; ++k)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) y ^= T.r[k][h].x ^ T.r[k][h].y;
-#pragma unroll
     for (int k = 0; k < NXP; ++k) x ^= T.rq[k].x ^ T.rq[k].y;
     asm volatile("" :: "v"(x), "v"(y));
 }
@@ -528,10 +453,6 @@ template <int R, int NXP>
 __device__ __forceinline__ void k_sink(const KTile<R, NXP, 1>& T) {   // loads-only ablation
     uint32_t x = T.a.x ^ T.a.y ^ T.a.z ^ T.a.w;
     uint64_t y = T.cm[0].x ^ T.cm[0].y ^ T.cm[1].x ^ T.cm[1].y;
-#pragma unroll
-    for (int k = 0; k < R; ++k)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) y ^= T.r[k][h].x ^ T.r[k][h].y;
 #pragma unroll
     for (int k = 0; k < NXP; ++k) x ^= T.rq[k].x ^ T.rq[k].y ^ T.rq[k].z ^ T.rq[k].w;
     asm volatile("" :: "v"(x), "v"(y));
@@ -559,9 +480,10 @@ __device__ __forceinline__ void k_sink(const KTile<R, NXP, 0>& T) {   // loads-o
 template <int R, int NXP, int PK, int NW, int ABLATE>
 __device__ __forceinline__ void k_run(const PodDev& P, const GroupDev& G, const PodSink<ABLATE>& K,
                                       const PodClass& C, int64_t a, int64_t b, uint32_t lane) {
+    static_assert(PK == 0 || R == 0, "packed blocks hold no records");
     constexpr int W = (int)k_tile_weight(R, NXP, PK);    // block size, half-KB units (generic: at most)
     // VGPRs a tile slot holds: 4 per 16-B load, 2 per 8-B one (the packed small pair rows)
-    constexpr int L = PK == 2 ? (4 + 4 * R + NXP) : W / 2;
+    constexpr int L = PK == 2 ? (4 + NXP) : W / 2;
     // block words: a compile-time constant for the specialised (packed small) shapes, the
     // class's own for the generic pipelines
     const int64_t BW = PK == 2 ? (int64_t)W * KB_UNIT : (int64_t)C.wt * KB_UNIT;
@@ -991,21 +913,16 @@ __device__ __forceinline__ void decide_store(const GroupDev& G, const GroupNode&
 }
 }  // namespace
 
-// Every K1 pipeline: (packed, records, extra pairs) of the K classes (PodClass::kind).
-#define ESC_KRUN_SHAPES(PK)                                                     \
-    ESC_KRUN(PK, 0, 0) ESC_KRUN(PK, 0, 1) ESC_KRUN(PK, 0, 2) ESC_KRUN(PK, 0, 3) \
-    ESC_KRUN(PK, 1, 0) ESC_KRUN(PK, 1, 1) ESC_KRUN(PK, 1, 2) ESC_KRUN(PK, 1, 3) \
-    ESC_KRUN(PK, 2, 0) ESC_KRUN(PK, 2, 1) ESC_KRUN(PK, 2, 2) ESC_KRUN(PK, 2, 3) \
-    ESC_KRUN(PK, 3, 0) ESC_KRUN(PK, 3, 1) ESC_KRUN(PK, 3, 2) ESC_KRUN(PK, 3, 3)
+// Every K1 pipeline, by PodClass::kind (k_kind): the packed small blocks' four shapes (extra
+// pairs 0..3; no packed block has records) each have their own.
+#define ESC_KRUN_PK8 ESC_KRUN(2, 0, 0) ESC_KRUN(2, 0, 1) ESC_KRUN(2, 0, 2) ESC_KRUN(2, 0, 3)
 // plain blocks: one generic pipeline (k_load above) for the 16 plain kinds
 #define ESC_KRUN_PLAIN                                                                          \
     case 0: case 1: case 2: case 3: case 4: case 5: case 6: case 7:                            \
     case 8: case 9: case 10: case 11: case 12: case 13: case 14: ESC_KRUN(0, 3, 3)   /* = case 15 */
-// packed (12-B) blocks: one generic pipeline for their 16 kinds too
-#define ESC_KRUN_PK1                                                                            \
-    case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23:                    \
-    case 24: case 25: case 26: case 27: case 28: case 29: case 30: ESC_KRUN(1, 3, 3)   /* = case 31 */
-#define ESC_KRUN_ALL ESC_KRUN_SHAPES(2) ESC_KRUN_PK1 ESC_KRUN_PLAIN
+// packed (12-B) blocks: one generic pipeline for their 4 kinds too
+#define ESC_KRUN_PK1 case 16: case 17: case 18: ESC_KRUN(1, 0, 3)   /* = case 19 */
+#define ESC_KRUN_ALL ESC_KRUN_PK8 ESC_KRUN_PK1 ESC_KRUN_PLAIN
 // LDS copies of the slot partials per K1 workgroup: K1_REPS when the window's slots are few
 // (lane l adds to copy l % K1_REPS, so lanes of one wave that hit the same slot mostly hit
 // different addresses — and, the copies 2 words apart mod the bank count, different banks;
@@ -1059,7 +976,7 @@ __global__ __launch_bounds__(THREADS) void k_pod_reduce(PodDev P, GroupDev G, in
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     __syncthreads();                                     // the partials are zeroed
 #define ESC_KRUN(PK, RR, XX) \
-    case PK * 16 + RR * 4 + XX: k_run<RR, XX, PK, NW, ABLATE>(P, G, K, C, a, b, lane); break;
+    case k_kind(RR, XX, PK): k_run<RR, XX, PK, NW, ABLATE>(P, G, K, C, a, b, lane); break;
     // the host's work plan: this workgroup's class runs, every wave interleaved over each
     typedef __attribute__((address_space(4))) const int64_t ci64;
     if (P.seg && !(ABLATE & 2)) {
@@ -1313,12 +1230,12 @@ __device__ __forceinline__ void k_tile_exact(const PodDev& P, const GroupDev& G,
         const uint32_t s = lane * PODS_PER_LANE + j;
         const KHead h = kb_head(C, P.kb, blk, s);
         if (h.flags & ESC_PF_DAEMONSET) continue;
-        uint64_t cpu = (uint64_t)h.cpu0, mem = (uint64_t)h.mem0;
-        for (uint32_t k = 0; k < R; ++k) {
-            int64_t rc, rm;
-            kb_rec(C, P.kb, blk, k, s, rc, rm);
-            apply_rec(k, R, C.xreg, C.xreg + C.xinit, (unsigned long long)rc, (unsigned long long)rm, cpu, mem);
-        }
+        // a plain pod's records (its flags carry their counts; a packed pod has none and
+        // its head is its request already)
+        int64_t rc[3] = {0, 0, 0}, rm[3] = {0, 0, 0}, cpu, mem;
+        for (uint32_t k = 0; k < R && k < 3; ++k) kb_rec(C, P.kb, blk, k, s, rc[k], rm[k]);
+        uint32_t o = 0;
+        pod_request(h.flags, (uint32_t)h.cpu0, h.mem0, rc, rm, o, cpu, mem);
         if (pf_default_ok(h.flags) && G.default_group != NONE) acc.add(G.n_gp, (int64_t)cpu, (int64_t)mem);
         if (h.pair0 < G.n_gp) acc.add(h.pair0, (int64_t)cpu, (int64_t)mem);
         for (uint32_t k = 0; k < C.nxp; ++k) {

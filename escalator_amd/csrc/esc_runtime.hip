@@ -216,18 +216,20 @@ static_assert(CS_SLOTS * CS_REC <= 128 && CS_SLOTS * CS_XP <= 128, "a spare C ti
 constexpr uint32_t CS_FLAGS = ESC_PF_DAEMONSET | ESC_PF_HAS_OVH | (uint32_t)CS_XREG << ESC_PF_XREG_SHIFT |
                               (uint32_t)CS_XINIT << ESC_PF_XINIT_SHIFT | (uint32_t)CS_XP << ESC_PF_XPAIR_SHIFT;
 
-// K class of a pod: its record signature (at most 3 extra container
-// records and 3 extra pairs; -1: the C section) | packed << 7: 1 when its values fit the
-// packed block (kp_fits), 2 when they also fit the packed small block (kp8_fits, in a context
-// with fewer than KP8_PAIR_NONE group pairs).  xc_cpu / xc_mem: the pod's own records (null
-// when it has none).
+// K class of a pod, the one place that decides it: -1 for the C section (more
+// than 3 extra container records or more than 3 extra pairs); else the fold (kp_fold) either
+// packs the pod's effective request — class id = its pair count np | packed << 7, packed 2
+// for the packed small block and 1 for the packed block, a signature without records — or
+// leaves the pod its records in the plain class of its own signature.  xc_cpu / xc_mem: the
+// pod's own records (null when it has none).
 int pod_class_id(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
                  const int64_t* xc_mem, uint32_t n_gp) {
     const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, np = pf_xpair(f);
     if (xr + xi + ov > 3 || np > 3) return -1;
-    const int sig = (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
-    if (!kp_fits(f, cpu0, mem0, pair0, xc_cpu, xc_mem)) return sig;
-    return sig | (n_gp < KP8_PAIR_NONE && kp8_fits(cpu0, mem0) ? 2 : 1) * POD_SIG_IDS;
+    int64_t cpu, mem;
+    const uint32_t packed = kp_fold(f, cpu0, mem0, pair0, xc_cpu, xc_mem, n_gp, cpu, mem);
+    if (packed) return (int)(np | packed * POD_SIG_IDS);
+    return (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
 }
 
 // The exchange buffer (SUM across ranks, reduce-scattered to the owners): the pods' words
@@ -1366,9 +1368,9 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     // signature, in 256-pod tiles whose records sit in per-tile rows; the rest go to 64-pod C
     // tiles with per-tile record offsets.  Sums are order-independent, so the placement
     // changes no result.  Padding pods carry ESC_PF_DAEMONSET, padding records are 0 and
-    // padding pairs NONE.  class id = record signature | packed << 7 (the pod's values fit the
-    // packed block, esc_kernels.h kp_fits; the packed class is listed first so that K1
-    // streams it first)
+    // padding pairs NONE.  class id = record signature | packed << 7 (pod_class_id: a packed
+    // pod's records are folded into its request, so its signature has none; the packed
+    // classes are listed first so that K1 streams them first)
     hvec<int16_t> pid(n);
     std::vector<std::vector<int64_t>> ch_cnt(TT, std::vector<int64_t>(POD_CLASS_IDS, 0));
     std::vector<int64_t> ch_nc(TT + 1, 0);
@@ -1419,8 +1421,9 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
         const int id = POD_CLASS_IDS - POD_SIG_IDS * (ord / POD_SIG_IDS + 1) + ord % POD_SIG_IDS;   // small, packed, plain
         const int sig = id % POD_SIG_IDS;
         // with spare slots requested every signature the K layout can hold gets a class, so
-        // that inserts of shapes absent at load still land in place
-        const bool holdable = (sig / 32) + ((sig / 8) % 4) + ((sig / 4) % 2) <= 3;
+        // that inserts of shapes absent at load still land in place (plain: every signature of
+        // at most 3 records; packed: the 4 without records)
+        const bool holdable = id < POD_SIG_IDS ? (sig / 32) + ((sig / 8) % 4) + ((sig / 4) % 2) <= 3 : sig < 4;
         if (!cnt[id] && !(c->spare_frac > 0 && holdable)) continue;
         PodClass k;
         std::memset(&k, 0, sizeof k);
@@ -1433,7 +1436,7 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
         const int64_t R = k.xreg + k.xinit + k.ovh, tiles = (want + TILE - 1) / TILE;
         k.t0 = kt;
         k.t1 = kt + tiles;
-        k.kind = (uint32_t)(k.packed * 16 + R * 4 + k.nxp);
+        k.kind = k_kind((uint32_t)R, k.nxp, k.packed);
         k.wt = k_tile_weight((uint32_t)R, k.nxp, k.packed);
         k.kb0 = kbw;
         k.w0 = kw;
@@ -1620,13 +1623,13 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     for (int64_t d = 0; d < npad; ++d)
         if (!(hf[d] & ESC_PF_DAEMONSET) || d < n_c) c->h_cused[d] = pf_xctr(hf[d]) | pf_xpair(hf[d]) << 16;
     c->live_pods = n;
-    c->live_xc = p->n_xc;
+    c->live_xc = (int64_t)sc_c;                       // records K1 streams: the C pods' and the plain K pods'
     c->live_xp = p->n_xp;
-    c->live_pk_pods = c->live_pk_xc = c->live_p8_pods = c->live_p8_xp = 0;
-    for (int id = POD_SIG_IDS; id < POD_CLASS_IDS; ++id) {
+    c->live_pk_pods = c->live_p8_pods = c->live_p8_xp = 0;
+    for (int id = 0; id < POD_CLASS_IDS; ++id) {
         if (cls_of[id] < 0) continue;
+        if (id < POD_SIG_IDS) { c->live_xc += cnt[id] * (int64_t)kb_nrec(cls[cls_of[id]]); continue; }
         c->live_pk_pods += cnt[id];
-        c->live_pk_xc += cnt[id] * (int64_t)kb_nrec(cls[cls_of[id]]);
         if (id >= 2 * POD_SIG_IDS) { c->live_p8_pods += cnt[id]; c->live_p8_xp += cnt[id] * (int64_t)cls[cls_of[id]].nxp; }
     }
     c->n_pods = n;
@@ -1874,11 +1877,12 @@ int32_t esc_stream_bytes(const esc_ctx* c, int64_t* pod_bytes, int64_t* node_byt
     if (!c || !pod_bytes || !node_bytes) return ESC_E_INVAL;
     if (!c->pods_loaded || !c->nodes_loaded) return ESC_E_STATE;
     // K1: flags 4 + cpu0 4 + mem0 8 + pair0 4 per pod, 16 per extra container record,
-    // 4 per extra pair, 8 per C tile (record offsets); a pod of a packed class 12 B + 8 per
-    // record, of a packed small class 8 B + 8 per record + 2 per extra pair (esc_kernels.h,
-    // kp_*, kp8_*); K2: see plan_node_layout (esc_node_layout.h)
+    // 4 per extra pair, 8 per C tile (record offsets); a pod of a packed class 12 B, of a
+    // packed small class 8 B + 2 per extra pair, neither with records (live_xc counts the
+    // records stored: the folded ones are gone; esc_kernels.h, kp_*, kp8_*, kp_fold);
+    // K2: see plan_node_layout (esc_node_layout.h)
     *pod_bytes = c->live_pods * 20 + c->live_xc * 16 + c->live_xp * 4 + c->c_tiles_loaded * 8 - c->live_pk_pods * 8 -
-                 c->live_pk_xc * 8 - c->live_p8_pods * 4 - c->live_p8_xp * 2;
+                 c->live_p8_pods * 4 - c->live_p8_xp * 2;
     *node_bytes = c->node_bytes;
     return ESC_OK;
 }
@@ -2658,7 +2662,7 @@ void remove_pod(esc_ctx* c, int64_t id, Patches& P) {
         c->cls_free[ci].push_back(q);
         c->live_xc -= k.xreg + k.xinit + k.ovh;
         c->live_xp -= k.nxp;
-        if (k.packed) { --c->live_pk_pods; c->live_pk_xc -= k.xreg + k.xinit + k.ovh; }
+        if (k.packed) --c->live_pk_pods;
         if (k.packed == 2) { --c->live_p8_pods; c->live_p8_xp -= k.nxp; }
     }
     c->pod_cls[id] = -2;
@@ -3222,21 +3226,22 @@ int32_t upsert_apply(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, const
             const PodClass& k = c->h_cls[ci];
             c->live_xc -= k.xreg + k.xinit + k.ovh;
             c->live_xp -= k.nxp;
-            if (k.packed) { --c->live_pk_pods; c->live_pk_xc -= k.xreg + k.xinit + k.ovh; }
-        if (k.packed == 2) { --c->live_p8_pods; c->live_p8_xp -= k.nxp; }
+            if (k.packed) --c->live_pk_pods;
+            if (k.packed == 2) { --c->live_p8_pods; c->live_p8_xp -= k.nxp; }
         }
         const PodClass& k = c->h_cls[ci];
         const int64_t q = c->pod_pos[id], sl = q % TILE;
         const int64_t blk = kb_block(k, k.t0 + q / TILE);
-        const uint32_t f = p->flags[i], R = kb_nrec(k);
-        kb_write_pod(k, blk, sl, f, p->cpu0[i], p->mem0[i], p->pair0[i], R ? p->xc_cpu + rof[i] : nullptr,
-                     R ? p->xc_mem + rof[i] : nullptr, k.nxp ? p->xp_pair + pof[i] : nullptr,
+        // (R: the records the slot stores — none in a packed class, which takes the pod's folded)
+        const uint32_t f = p->flags[i], R = kb_nrec(k), nc = pf_xctr(f);
+        kb_write_pod(k, blk, sl, f, p->cpu0[i], p->mem0[i], p->pair0[i], nc ? p->xc_cpu + rof[i] : nullptr,
+                     nc ? p->xc_mem + rof[i] : nullptr, k.nxp ? p->xp_pair + pof[i] : nullptr,
                      [&](int width, int64_t at, uint64_t v) { P.add(pt_kb(width), at, v); });
         touch_grew |= touch_mark(c, ci, q, f, p->pair0[i], k.nxp ? p->xp_pair + pof[i] : nullptr);
         ++c->live_pods;
         c->live_xc += R;
         c->live_xp += k.nxp;
-        if (k.packed) { ++c->live_pk_pods; c->live_pk_xc += R; }
+        if (k.packed) ++c->live_pk_pods;
         if (k.packed == 2) { ++c->live_p8_pods; c->live_p8_xp += k.nxp; }
     }
     int32_t rc = apply_patches(c, P, pod_targets(c));

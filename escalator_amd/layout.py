@@ -5,9 +5,12 @@ K1 reads the pod shard once per decision: per pod flags 4 + cpu0 4 + mem0 8 + pa
 16 B per extra container record, 4 B per extra selector pair, and 8 B of record offsets
 per 64-pod C tile (pods with more than 3 extra container records or more than 3 extra
 pairs; all other pods sit in homogeneous 256-pod K tiles that need no offsets).  A K pod
-whose values fit the packed block (``packed_mask``) takes 12 B (pair0 | flags 4, cpu0 | mem0
-8) and 8 B per record; one that also fits the packed small block (``small_mask``) 8 B
-(cpu0 | mem0 | pair0 | flags in one u64), 8 B per record and 2 B per extra pair.
+whose own values fit the packed ranges (``fits_mask``) has its container records folded
+into one effective request at load (``folded_request``); when that request fits the packed
+block too (``packed_mask``) the pod takes 12 B (pair0 | flags 4, cpu | mem 8) and no record
+bytes, and when it also fits the packed small block (``small_mask``) 8 B (cpu | mem | pair0 |
+flags in one u64) and 2 B per extra pair.  A K pod whose fold leaves the packed ranges keeps
+its records in the plain layout.
 K2 reads the node index once per decision: per (label pair, node) entry of a pair some group
 selects 16 B when every node's allocatable cpu is in [0, 2^32) (one packed record: flags 4 +
 cpu 4 + mem 8), else 20 B (flags 4 + cpu 8 + mem 8), and 8 B per piece (offset + pair).
@@ -35,10 +38,10 @@ KP_PAIR_NONE = (1 << 28) - 1
 INT64_MIN = -(1 << 63)
 
 
-def packed_mask(pods: dict) -> np.ndarray:
-    """Pods of a K class whose values fit the packed block: cpu0 and every record cpu in
-    [0, 2^20 - 1), mem0 and every record mem in [0, 2^44 - 1) (an init container's key may be
-    absent, INT64_MIN, instead) and pair0 NONE or < 2^28 - 1."""
+def fits_mask(pods: dict) -> np.ndarray:
+    """Pods of a K class whose own values are in the packed ranges: cpu0 and every record cpu
+    in [0, 2^20 - 1), mem0 and every record mem in [0, 2^44 - 1) (an init container's key may
+    be absent, INT64_MIN, instead) and pair0 NONE or < 2^28 - 1."""
     f = np.asarray(pods["flags"], np.uint64)
     nreg, ninit = (f >> 8) & 0xFF, (f >> 16) & 0xFF
     nrec = (nreg + ninit + ((f >> 4) & 1)).astype(np.int64)
@@ -62,19 +65,67 @@ def packed_mask(pods: dict) -> np.ndarray:
     return ok
 
 
+def folded_request(pods: dict) -> tuple[np.ndarray, np.ndarray]:
+    """Every pod's effective (cpu, mem) request, ComputePodResourceRequest: the first
+    container plus the extra regular containers, the maximum of that and every init container
+    (an absent key, INT64_MIN, takes no part), plus the overhead.  Exact for the pods of
+    ``fits_mask`` (at most 4 values below 2^44 each: below 2^47); the others' may wrap and are
+    not used."""
+    f = np.asarray(pods["flags"], np.uint64)
+    nreg, ninit = ((f >> 8) & 0xFF).astype(np.int64), ((f >> 16) & 0xFF).astype(np.int64)
+    nrec = nreg + ninit + ((f >> 4) & 1).astype(np.int64)
+    cpu = np.asarray(pods["cpu0"], np.int64).copy()
+    mem = np.asarray(pods["mem0"], np.int64).copy()
+    n_rec = int(nrec.sum())
+    if not n_rec:
+        return cpu, mem
+    xc = np.asarray(pods["xc_cpu"], np.int64)[:n_rec]
+    xm = np.asarray(pods["xc_mem"], np.int64)[:n_rec]
+    owner = np.repeat(np.arange(len(f), dtype=np.int64), nrec)
+    k = np.arange(n_rec, dtype=np.int64) - np.repeat(np.cumsum(nrec) - nrec, nrec)
+    reg = k < nreg[owner]
+    ovh = k >= (nreg + ninit)[owner]
+    init = ~reg & ~ovh
+
+    def seg_sum(mask, counts):
+        """Per pod, the sum of its `counts` records under `mask` (they are consecutive)."""
+        c, m = np.concatenate([[0], np.cumsum(xc[mask])]), np.concatenate([[0], np.cumsum(xm[mask])])
+        end = np.cumsum(counts)
+        return c[end] - c[end - counts], m[end] - m[end - counts]
+
+    ac, am = seg_sum(reg, nreg)                          # the regular containers first,
+    cpu += ac
+    mem += am
+    has = ninit > 0                                      # then every init container,
+    if has.any():
+        start = (np.cumsum(ninit) - ninit)[has]
+        cpu[has] = np.maximum(cpu[has], np.maximum.reduceat(xc[init], start))
+        mem[has] = np.maximum(mem[has], np.maximum.reduceat(xm[init], start))
+    ac, am = seg_sum(ovh, nrec - nreg - ninit)           # then the overhead
+    cpu += ac
+    mem += am
+    return cpu, mem
+
+
+def packed_mask(pods: dict, _fold=None) -> np.ndarray:
+    """Pods stored in a packed block: their own values fit (``fits_mask``) and so does the
+    folded request, cpu in [0, 2^20 - 1) and mem in [0, 2^44 - 1)."""
+    cpu, mem = _fold or folded_request(pods)
+    return fits_mask(pods) & (cpu >= 0) & (cpu < KP_CPU_ABSENT) & (mem >= 0) & (mem < KP_MEM_ABSENT)
+
+
 KP8_CPU_MAX = (1 << 14) - 1       # packed small block (kp8_*): cpu0, mem0 ranges, pair-id field
 KP8_MEM_MAX = (1 << 34) - 1
 KP8_PAIR_NONE = (1 << 14) - 1
 
 
-def small_mask(pods: dict, n_gp: int) -> np.ndarray:
-    """Packed pods that also fit the packed small block: cpu0 < 2^14, mem0 < 2^34, in a
-    context with fewer than 2^14 - 1 group pairs."""
+def small_mask(pods: dict, n_gp: int, _fold=None) -> np.ndarray:
+    """Packed pods whose folded request also fits the packed small block: cpu < 2^14,
+    mem < 2^34, in a context with fewer than 2^14 - 1 group pairs."""
     if n_gp >= KP8_PAIR_NONE:
         return np.zeros(len(pods["flags"]), bool)
-    cpu0 = np.asarray(pods["cpu0"], np.int64)
-    mem0 = np.asarray(pods["mem0"], np.int64)
-    return packed_mask(pods) & (cpu0 <= KP8_CPU_MAX) & (mem0 >= 0) & (mem0 <= KP8_MEM_MAX)
+    cpu, mem = fold = _fold or folded_request(pods)
+    return packed_mask(pods, fold) & (cpu >= 0) & (cpu <= KP8_CPU_MAX) & (mem >= 0) & (mem <= KP8_MEM_MAX)
 
 
 def pod_bytes(pods: dict, n_gp: int, lo: int = 0, hi: int | None = None) -> int:
@@ -84,12 +135,13 @@ def pod_bytes(pods: dict, n_gp: int, lo: int = 0, hi: int | None = None) -> int:
     hi = len(f) if hi is None else hi
     nrec = (((f >> 8) & 0xFF) + ((f >> 16) & 0xFF) + ((f >> 4) & 1)).astype(np.int64)[lo:hi]
     nxp = ((f >> 24) & 0x3F).astype(np.int64)[lo:hi]
-    pk = packed_mask(pods)[lo:hi]
-    sm = small_mask(pods, n_gp)[lo:hi]
+    fold = folded_request(pods)
+    pk = packed_mask(pods, fold)[lo:hi]
+    sm = small_mask(pods, n_gp, fold)[lo:hi]
     c_tiles = (complex_pods(f[lo:hi]) + 63) // 64
     plain = (20 + 16 * nrec + 4 * nxp)[~pk].sum()
-    packed = (12 + 8 * nrec + 4 * nxp)[pk & ~sm].sum()
-    small = (8 + 8 * nrec + 2 * nxp)[sm].sum()
+    packed = (12 + 4 * nxp)[pk & ~sm].sum()           # a packed pod's records are folded away
+    small = (8 + 2 * nxp)[sm].sum()
     return int(plain + packed + small + c_tiles * 8)
 
 

@@ -488,8 +488,12 @@ int32_t esc_hbm_probe(esc_ctx* ctx, int64_t bytes, int32_t reps, double* read_gb
  * (the reference re-lists every pod and node per group per decision through its
  * informer caches, pkg/k8s/cache.go:16-56 -> pod_listers.go:33, node_listers.go:33).
  * Pod ids are the indices of esc_load_pods' input; new ids (< 2^31) insert.  A pod
- * lands in the spare slots of its record-signature class (esc_set_spare, before the
- * load, reserves them); a pod with > 3 container records or > 3 extra pairs (or whose
+ * lands in the spare slots of its class (esc_set_spare, before the load, reserves them):
+ * a pod whose values and whose effective request (ComputePodResourceRequest, evaluated
+ * once, at the load or the upsert: a pod's container requests do not change without an
+ * event) fit the packed ranges is stored as that one request in the packed class of its
+ * pair count, every other pod with its records in the class of its record signature; a
+ * pod with > 3 container records or > 3 extra pairs (or whose
  * class is full) stays in its own C-section slot when that has room, else takes a spare
  * C slot (room for 4 extra regular and 2 init containers, an overhead and 6 extra pairs;
  * unused records stay neutral).  A batch that does not fit in place returns ESC_E_LIMIT
