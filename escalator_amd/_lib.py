@@ -185,6 +185,8 @@ _SIGS = {
     "esc_set_spare": (i32, [VP, dbl]),
     "esc_pods_upsert": (i32, [VP, P(i64), P(PodSoA)]),
     "esc_pods_delete": (i32, [VP, P(i64), i64]),
+    "esc_pods_grow": (i32, [VP, P(i64), P(PodSoA)]),
+    "esc_pods_room": (i32, [VP, P(i64), P(i64), P(i64), P(i64)]),
     "esc_nodes_update": (i32, [VP, P(i64), i64, P(u32), P(i64), P(i64)]),
     "esc_nodes_add": (i32, [VP, P(NodeSoA), P(i64)]),
     "esc_nodes_delete": (i32, [VP, P(i64), i64]),

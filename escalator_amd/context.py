@@ -277,6 +277,28 @@ class Context:
             L.check(rc, "esc_pods_upsert")
         return rc
 
+    def pods_grow(self, ids=None, pods: dict | None = None):
+        """The pod classes grown on the device (esc_pods_grow) so that ``pods_upsert(ids, pods)``
+        made right after it cannot answer ESC_E_LIMIT; without a batch only the spare fraction
+        over the live counts is restored.  Pod ids, classes, positions and the placement stay.
+        EscError(ESC_E_LIMIT) for a batch pod no spare C slot can hold (reload)."""
+        if pods is None or len(pods["flags"]) == 0:
+            L.check(self.lib.esc_pods_grow(self.handle, None, None), "esc_pods_grow")
+            return
+        ids = np.ascontiguousarray(ids, np.int64)
+        ps, keep = pod_soa(pods)
+        L.check(self.lib.esc_pods_grow(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ps)),
+                "esc_pods_grow")
+
+    def pods_room(self) -> dict:
+        """esc_pods_room: ``k_capacity`` (K positions in all), ``k_free``, ``c_free`` (free C
+        slots) and ``per_class`` (int64[384] by class id: free positions, -1 without a class)."""
+        a, b, d = C.c_int64(), C.c_int64(), C.c_int64()
+        per = np.zeros(384, np.int64)
+        L.check(self.lib.esc_pods_room(self.handle, C.byref(a), C.byref(b), C.byref(d),
+                                       per.ctypes.data_as(C.POINTER(C.c_int64))), "esc_pods_room")
+        return {"k_capacity": a.value, "k_free": b.value, "c_free": d.value, "per_class": per}
+
     def pods_delete(self, ids):
         ids = np.ascontiguousarray(ids, np.int64)
         L.check(self.lib.esc_pods_delete(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids)),

@@ -2,6 +2,7 @@
 //   esc_runtime.hip   the context, the decision step, the loaders, the ordering, the events,
 //                     reaping
 //   esc_rebuild.hip   the device rebuild of the node side, the node table's compaction, the audit
+//   esc_pod_grow.hip  the pod classes grown on the device (esc_pods_grow, esc_pods_room)
 // Everything else (esc_multi.hip, esc_list.hip, the packer, the generator) sees esc_ctx as
 // opaque.  Helpers that cross a file are declared at the end, each defined in the file of its
 // subsystem; the small ones are inline here.
@@ -27,6 +28,7 @@
 #include "esc_kernels.h"
 #include "esc_multi.h"
 #include "esc_node_layout.h"
+#include "esc_pod_layout.h"
 
 #ifndef ESC_MEASURE
 #define ESC_MEASURE 0   // 1: the measurement library (Makefile ABLATIONS=1) reads its knobs
@@ -257,6 +259,7 @@ struct esc_ctx {
     // next n ordering / listing launches give up their look-back at once, the next n event
     // patch applications fail after their host-side writes
     int lb_fail_order = 0, lb_fail_list = 0, fail_patches = 0;
+    int fail_grow = 0;                                        // the next n esc_pods_grow fail before their swap
     uint32_t *d_pstart = nullptr, *d_plen = nullptr;
     uint32_t* d_ord = nullptr;                                // K5 output, in the group regions
     esc::OrdChunk* d_pchunks = nullptr;                       // packed chunks of small groups
@@ -289,7 +292,8 @@ struct esc_ctx {
     // incremental snapshot (§8f rank 1): where each loaded pod lives, free K slots
     double spare_frac = 0.0;                                  // esc_set_spare
     esc::hvec<int32_t> pod_cls;                               // by pod id: K class index, -1 C, -2 absent
-    esc::hvec<int64_t> pod_pos;                               // K: position in its class; C: base-array index
+    esc::hvec<int64_t> pod_pos;                               // K: position in its class; C: C-array index (slot
+                                                              // k_tiles * 256 + it: a grown K section moves no C pod)
     std::vector<std::vector<int64_t>> cls_free;               // per K class: free positions
     std::vector<esc::PodClass> h_cls;
     std::vector<int> h_cls_of;                                // signature id -> class index (-1: none)
@@ -298,6 +302,7 @@ struct esc_ctx {
     std::vector<uint32_t> h_cused;                            // a C slot's pod's own records | pairs << 16
     std::vector<uint32_t> h_xc_base, h_xp_base;               // C tiles' record / pair offsets
     int64_t live_pods = 0, live_xc = 0, live_xp = 0;
+    int64_t live_c_pods = 0;                    // of them in C slots (their own, or parked there by a full class)
     int64_t live_pk_pods = 0;                   // of them in packed K classes (either size; no records there)
     int64_t live_p8_pods = 0, live_p8_xp = 0;   // of them in packed small K classes, their extra pairs
     int64_t c_tiles_loaded = 0;                 // C tiles of loaded pods (the spare C tiles excluded)
@@ -421,5 +426,22 @@ void commit_layout(esc_ctx* c, NodeLayout& L, bool pk_ok);
 RemovalDev occ_dev(const esc_ctx* c);
 int32_t ensure_ne_dev(esc_ctx* c);
 int32_t occ_recount(esc_ctx* c);
+void release_work(esc_ctx* c);
+int32_t ensure_work(esc_ctx* c);
+// A pod event batch as esc_pods_upsert and esc_pods_grow both read it: validated, each pod's
+// first record / extra pair in the batch and its class id (pod_class_id).
+struct BatchShape {
+    std::vector<int64_t> rof, pof;
+    std::vector<int16_t> sid;
+};
+int32_t batch_shape(const esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, BatchShape& b);
+// Does batch pod `id`, bound for K class ci, need a new position there (no: it is in ci already)?
+inline bool k_needs_pos(const esc_ctx* c, int64_t id, int ci) {
+    return !(id < (int64_t)c->pod_cls.size() && c->pod_cls[id] == ci);
+}
+// Does batch pod `id` with flags f, bound for the C section, stay in its own C slot?
+inline bool c_keeps_slot(const esc_ctx* c, int64_t id, uint32_t f) {
+    return id < (int64_t)c->pod_cls.size() && c->pod_cls[id] == -1 && c_room(c->h_cflags[c->pod_pos[id]], f);
+}
 
 }  // namespace esc

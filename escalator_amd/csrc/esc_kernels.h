@@ -5,271 +5,14 @@
 #include <stdint.h>
 
 #include "esc_common.h"
+#include "esc_kblock.h"
 
 namespace esc {
-
-// A class of homogeneous pod tiles: every pod of the class has the same record
-// signature (extra regular containers, init containers, overhead, extra pairs), so every
-// field and record k of a tile's 256 pods is one contiguous 256-entry row.
-struct PodClass {
-    int64_t t0, t1;            // tiles [t0, t1) of the K section
-    int64_t kb0, rsv;          // u32-word offset of tile t0's block in the K-block array
-    int64_t w0;                // K1 work weight of the tiles before t0
-    uint32_t xreg, xinit, ovh, nxp;
-    uint32_t kind;             // selects K1's pipeline: plain (xreg + xinit + ovh) * 4 + nxp, packed 16 + nxp,
-                               // packed small 20 + nxp (a packed class has no records: kp_fold)
-    uint32_t wt;               // work weight of one tile: its 16-B loads per lane (= block KB)
-    uint32_t packed;           // 0 plain, 1 packed (12 B / pod), 2 packed small (8 B / pod): kp_*, kp8_* below
-    uint32_t pad;
-};
-// weight of a K tile with R records and NXP extra pairs per pod: its block size in half-KB
-// units (128 u32 words; the packed small block's u16 pair rows are half a KB each).  Packed
-// tiles hold no records (R is the plain layout's alone).
-constexpr uint32_t k_tile_weight(uint32_t R, uint32_t NXP, uint32_t packed = 0) {
-    return packed == 2 ? 4 + NXP : (packed ? 2 * (3 + NXP) : 2 * (5 + 4 * R + NXP));
-}
-constexpr uint32_t k_kind(uint32_t R, uint32_t NXP, uint32_t packed) {
-    return packed ? 16 + (packed - 1) * 4 + NXP : R * 4 + NXP;
-}
-constexpr uint32_t K_TILE_WEIGHT_MIN = 4;   // the lightest tile (packed small, no records or pairs)
-constexpr int64_t KB_UNIT = 128;            // u32 words per weight unit
-constexpr int POD_SIG_IDS = 128;     // signatures with <= 3 extra records and <= 3 extra pairs
-constexpr int POD_CLASS_IDS = 384;   // class id = signature | packed << 7
-constexpr int K1_SEGS = 4;           // class runs per K1 workgroup in the work plan (at most)
-
-// K blocks (tile-major K section).  Tile t of a class is ONE contiguous block of wt KB
-// (wt = 5 + 4R + NXP): a wave streams a tile as wt consecutive 1-KB wave-loads from one
-// address range instead of wt loads from 4 + 2R + 1 separate arrays (the SoA streams cost
-// 6.5 % at 100 M pods and 4 % at 12.5 M in scripts/k1_shape_probe.hip, profiles/r02_v8).
-// Word offsets inside a block (u32 words; 8-byte rows are 512 words = 256 entries):
-//   flags [0, 256)  cpu0 [256, 512)  mem0 [512, 1024)  pair0 [1024, 1280)
-//   record k: cpu [1280 + 1024k, +512), mem [+512, +1024)   extra pair k: [1280 + 1024R + 256k, +256)
-// 4-byte rows hold pod s at entry s; 8-byte rows at pos64(s) = (s%4/2)*128 + 2(s/4) + s%2,
-// so that lane l's 16-B load of either width covers its pods 4l..4l+3 and every wave-load
-// reads one contiguous 1 KB.
-constexpr int KB_CPU0 = 256, KB_MEM0 = 512, KB_PAIR0 = 1024, KB_REC = 1280;
-__host__ __device__ inline int64_t kb_pos64(int64_t s) { return ((s & 3) >> 1) * 128 + 2 * (s >> 2) + (s & 1); }
-// first word of tile t's block (t a tile of class C)
-__host__ __device__ inline int64_t kb_block(const PodClass& C, int64_t t) { return C.kb0 + (t - C.t0) * (int64_t)C.wt * KB_UNIT; }
-__host__ __device__ inline uint32_t kb_nrec(const PodClass& C) { return C.xreg + C.xinit + C.ovh; }
-// 8-byte element index (into the array viewed as int64) of record k's cpu (mem: +256) of pod s
-__host__ __device__ inline int64_t kb_rec64(int64_t blk, uint32_t k, int64_t s) {
-    return (blk + KB_REC + 1024 * (int64_t)k) / 2 + kb_pos64(s);
-}
-// Packed K blocks (PodClass::packed): the same tile-major block with the pod's effective
-// request — its container records folded into one (cpu, mem) on the host, kp_fold below —
-// packed into 12 B per pod instead of 20 + 16 per record:
-//   word  [0, 256)            pair0 (bits 0..27, KP_PAIR_NONE = no pair) | the pod's own flag
-//                             bits DAEMONSET, STATIC, HAS_SEL, AFF_BLOCK at bits 28..31 (every
-//                             other flag bit is the class signature's)
-//   u64   [256, 768)          cpu | mem << 20 at kb_pos64(s): the effective request
-//   u32   extra pair k        [768 + 256k, +256), as in the plain layout
-// A pod is packed when cpu0 and every record cpu are in [0, 2^20 - 1), mem0 and every record
-// mem in [0, 2^44 - 1) (an init record's key may instead be absent), pair0 < 2^28 - 1
-// (kp_fits) and its effective request is in the same ranges — the range of K1's LDS fast
-// path.  A packed class has no records (signature (0, 0, 0, nxp)); every other K pod keeps
-// its records in the plain layout of its own signature.
-constexpr int KP_CM0 = 256, KP_XP = 768;
-constexpr uint32_t KP_FLAG_SHIFT = 28;
-constexpr uint32_t KP_PAIR_NONE = (1u << KP_FLAG_SHIFT) - 1;
-constexpr uint32_t KP_POD_FLAGS = ESC_PF_DAEMONSET | ESC_PF_STATIC | ESC_PF_HAS_SEL | ESC_PF_AFF_BLOCK;
-constexpr int KP_CPU_BITS = 20;
-// the fields' masks and the exclusive bounds of the packed ranges (the names are from the
-// all-ones sentinel a packed init record's absent key had; no record is stored now)
-constexpr uint64_t KP_CPU_ABSENT = (uint64_t(1) << KP_CPU_BITS) - 1;
-constexpr uint64_t KP_MEM_ABSENT = (uint64_t(1) << 44) - 1;
-// Packed small K blocks (PodClass::packed == 2): a packed pod whose effective request also
-// has cpu < 2^14 m and mem < 2^34 B (16 cores, 16 GiB: most pods), in a context with fewer
-// than 2^14 - 1 group pairs, is ONE u64 (8 B):
-//   u64   [0, 512)            cpu | mem << 14 | pair0 << 48 (14 bits; KP8_PAIR_NONE: no
-//                             pair, or one no group selects) | daemonset << 62 |
-//                             blocks-default << 63 (static, has-selector or affinity: the
-//                             default filter's other conditions, node_group.go:263-273)
-//                             A daemonset pod (and a free slot) is stored with no pairs and
-//                             blocks-default set, so K1 adds it nowhere without a test.
-//   u16   extra pair k        [512 + 128k, +128) words: pod s at u16 index s (0xFFFF: none,
-//                             or one no group selects)
-constexpr int KP8_XP = 512;
-constexpr int KP8_CPU_BITS = 14, KP8_MEM_BITS = 34, KP8_PAIR_SHIFT = 48;
-constexpr uint64_t KP8_CPU_MASK = (uint64_t(1) << KP8_CPU_BITS) - 1;
-constexpr uint64_t KP8_MEM_MASK = (uint64_t(1) << KP8_MEM_BITS) - 1;
-constexpr uint32_t KP8_PAIR_NONE = (1u << 14) - 1;
-constexpr uint64_t KP8_DS = uint64_t(1) << 62, KP8_NODEF = uint64_t(1) << 63;
-__host__ __device__ inline bool kp8_fits(int64_t cpu, int64_t mem) {
-    return cpu >= 0 && (uint64_t)cpu <= KP8_CPU_MASK && mem >= 0 && (uint64_t)mem <= KP8_MEM_MASK;
-}
-__host__ __device__ inline uint64_t kp8_word(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0) {
-    const bool ds = (f & ESC_PF_DAEMONSET) != 0;
-    const uint64_t q = pair0 < KP8_PAIR_NONE && !ds ? pair0 : KP8_PAIR_NONE;
-    return (uint64_t)cpu0 | (uint64_t)mem0 << KP8_CPU_BITS | q << KP8_PAIR_SHIFT | (ds ? KP8_DS | KP8_NODEF : 0) |
-           ((f & (ESC_PF_STATIC | ESC_PF_HAS_SEL | ESC_PF_AFF_BLOCK)) ? KP8_NODEF : 0);
-}
-// extra pair k of pod s: its u32-word index (plain and packed blocks) or, in a packed small
-// block, its u16 index (kb_pair reads either)
-constexpr uint32_t KP8_XP_NONE = 0xFFFFu;
-__host__ __device__ inline int64_t kb_xp(const PodClass& C, int64_t blk, uint32_t k, int64_t s) {
-    if (C.packed == 2) return (blk + KP8_XP + 128 * (int64_t)k) * 2 + s;
-    if (C.packed) return blk + KP_XP + 256 * (int64_t)k + s;
-    return blk + KB_REC + 1024 * (int64_t)kb_nrec(C) + 256 * (int64_t)k + s;
-}
-// the first u32 word of the extra-pair rows of the block at blk, and their size in words
-__host__ __device__ inline int64_t kb_xp_row0(const PodClass& C, int64_t blk) {
-    if (C.packed == 2) return blk + KP8_XP;
-    return kb_xp(C, blk, 0, 0);
-}
-__host__ __device__ inline int64_t kb_xp_words(const PodClass& C) { return (int64_t)C.nxp * (C.packed == 2 ? 128 : 256); }
-__host__ __device__ inline uint32_t kb_pair(const PodClass& C, const uint32_t* kb, int64_t blk, uint32_t k, int64_t s) {
-    if (C.packed == 2) {
-        const uint32_t q = reinterpret_cast<const uint16_t*>(kb)[kb_xp(C, blk, k, s)];
-        return q == KP8_XP_NONE ? NONE : q;
-    }
-    return kb[kb_xp(C, blk, k, s)];
-}
-// A freed / padding slot: daemonset-flagged, no pair (put as in kb_write_pod below).
-// put(width, index, value): width 8 = int64 element index, 4 = u32 word, 2 = u16 element.
-template <class Put>
-__host__ __device__ inline void kb_write_free(const PodClass& C, int64_t blk, int64_t sl, Put&& put) {
-    if (C.packed == 2) {
-        put(8, blk / 2 + kb_pos64(sl), KP8_DS | KP8_NODEF | (uint64_t)KP8_PAIR_NONE << KP8_PAIR_SHIFT);
-        for (uint32_t k = 0; k < C.nxp; ++k) put(2, kb_xp(C, blk, k, sl), KP8_XP_NONE);   // no pairs (see kp8_word)
-    } else {
-        put(4, blk + sl, C.packed ? (ESC_PF_DAEMONSET << KP_FLAG_SHIFT) | KP_PAIR_NONE : ESC_PF_DAEMONSET);
-    }
-}
-// Is a (cpu, mem) pair inside the packed ranges?  (init: an init container's record, whose
-// absent key, INT64_MIN, is allowed.)
-__host__ __device__ inline bool kp_val_fits(int64_t cpu, int64_t mem, bool init) {
-    const bool c = (cpu >= 0 && (uint64_t)cpu < KP_CPU_ABSENT) || (init && cpu == INT64_MIN);
-    const bool m = (mem >= 0 && (uint64_t)mem < KP_MEM_ABSENT) || (init && mem == INT64_MIN);
-    return c && m;
-}
-// packed 8-byte value of an effective request inside the packed ranges
-__host__ __device__ inline uint64_t kp_val(int64_t cpu, int64_t mem) { return (uint64_t)cpu | ((uint64_t)mem << KP_CPU_BITS); }
-__host__ __device__ inline int64_t kp_cpu(uint64_t v) { return (int64_t)(v & KP_CPU_ABSENT); }
-__host__ __device__ inline int64_t kp_mem(uint64_t v) { return (int64_t)(v >> KP_CPU_BITS); }
-__host__ __device__ inline uint32_t kp_word(uint32_t flags, uint32_t pair0) {
-    return ((flags & KP_POD_FLAGS) << KP_FLAG_SHIFT) | (pair0 == NONE ? KP_PAIR_NONE : pair0);
-}
-__host__ __device__ inline uint32_t kp_pair0(uint32_t w) {
-    const uint32_t q = w & KP_PAIR_NONE;
-    return q == KP_PAIR_NONE ? NONE : q;
-}
-// full ESC_PF_* flags of a packed pod as stored: its own bits + the class signature (which
-// has no records: the pod reads back as one container with its effective request)
-__host__ __device__ inline uint32_t kp_flags(const PodClass& C, uint32_t w) {
-    return (w >> KP_FLAG_SHIFT) | (C.nxp << ESC_PF_XPAIR_SHIFT);
-}
-// Are the pod's own values all inside the packed ranges?  (xc_cpu / xc_mem: its extra
-// records, regular, then init, then overhead, as esc_pod_soa lists them.)
-__host__ __device__ inline bool kp_fits(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
-                                        const int64_t* xc_mem) {
-    if (!(pair0 == NONE || pair0 < KP_PAIR_NONE) || !kp_val_fits((int64_t)cpu0, mem0, false)) return false;
-    const uint32_t nreg = pf_xreg(f), ninit = pf_xinit(f), n = pf_xctr(f);
-    for (uint32_t k = 0; k < n; ++k)
-        if (!kp_val_fits(xc_cpu[k], xc_mem[k], k >= nreg && k < nreg + ninit)) return false;
-    return true;
-}
-// The fold: a K-section pod whose values pass kp_fits has its effective request
-// (pod_request, esc_common.h) computed once on the host — its container requests are fixed for
-// the pod's life; a change arrives as an upsert, which rewrites the slot.  Every value is
-// then in [0, 2^44) and there are at most 4 of them, so the request is in [0, 2^47): nothing
-// wraps.  Returns the layout the pod takes, with the request in cpu / mem: 2 the packed small
-// block (in a context of n_gp < KP8_PAIR_NONE group pairs), 1 the packed block, 0 the plain
-// block of its own signature, records kept (kp_fits failed, or the request is outside the
-// packed ranges; cpu / mem are then not meaningful).
-__host__ __device__ inline uint32_t kp_fold(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
-                                            const int64_t* xc_mem, uint32_t n_gp, int64_t& cpu, int64_t& mem) {
-    cpu = (int64_t)cpu0;
-    mem = mem0;
-    if (!kp_fits(f, cpu0, mem0, pair0, xc_cpu, xc_mem)) return 0;
-    uint32_t o = 0;
-    pod_request(f, cpu0, mem0, xc_cpu, xc_mem, o, cpu, mem);
-    if (n_gp < KP8_PAIR_NONE && kp8_fits(cpu, mem)) return 2;
-    return kp_val_fits(cpu, mem, false) ? 1 : 0;
-}
-// The head of K pod s of the block at word blk, any layout: ESC_PF_* flags (the class
-// signature's counts included; a packed small pod's static / has-selector / affinity bits
-// read back as ESC_PF_HAS_SEL), pair0 (NONE: none, or no group's in a small block) and the
-// first container's cpu / mem (a packed pod's: its effective request); kb_rec: record k's
-// cpu / mem of a plain pod (an absent init key INT64_MIN; packed classes have no records).
-struct KHead {
-    uint32_t flags, pair0;
-    int64_t cpu0, mem0;
-};
-__host__ __device__ inline KHead kb_head(const PodClass& C, const uint32_t* kb, int64_t blk, int64_t s) {
-    KHead h;
-    const int64_t* kb64 = reinterpret_cast<const int64_t*>(kb);
-    if (C.packed == 2) {
-        const uint64_t w = (uint64_t)kb64[blk / 2 + kb_pos64(s)];
-        h.flags = kp_flags(C, 0) | ((w & KP8_DS) ? ESC_PF_DAEMONSET : 0u) | ((w & KP8_NODEF) ? ESC_PF_HAS_SEL : 0u);
-        const uint32_t q = (uint32_t)(w >> KP8_PAIR_SHIFT) & KP8_PAIR_NONE;
-        h.pair0 = q == KP8_PAIR_NONE ? NONE : q;
-        h.cpu0 = (int64_t)(w & KP8_CPU_MASK);
-        h.mem0 = (int64_t)((w >> KP8_CPU_BITS) & KP8_MEM_MASK);
-    } else if (C.packed) {
-        const uint32_t w0 = kb[blk + s];
-        const uint64_t v = (uint64_t)kb64[(blk + KP_CM0) / 2 + kb_pos64(s)];
-        h.flags = kp_flags(C, w0);
-        h.pair0 = kp_pair0(w0);
-        h.cpu0 = kp_cpu(v);
-        h.mem0 = kp_mem(v);
-    } else {
-        h.flags = kb[blk + s];
-        h.pair0 = kb[blk + KB_PAIR0 + s];
-        h.cpu0 = kb[blk + KB_CPU0 + s];
-        h.mem0 = kb64[(blk + KB_MEM0) / 2 + kb_pos64(s)];
-    }
-    return h;
-}
-__host__ __device__ inline void kb_rec(const PodClass& C, const uint32_t* kb, int64_t blk, uint32_t k, int64_t s,
-                                       int64_t& cpu, int64_t& mem) {
-    const int64_t* kb64 = reinterpret_cast<const int64_t*>(kb);
-    const int64_t o = kb_rec64(blk, k, s);
-    cpu = kb64[o];
-    mem = kb64[o + 256];
-}
-
-// Every word a K-class pod occupies in its tile (load and in-place upserts): put(width,
-// index, value) as for kb_write_free.  xc_cpu / xc_mem are the pod's own records (by its
-// flags f); a packed class stores their fold (the class kp_fold chose for the pod).
-template <class Put>
-__host__ __device__ inline void kb_write_pod(const PodClass& C, int64_t blk, int64_t sl, uint32_t f, uint32_t cpu0,
-                                             int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
-                                             const int64_t* xc_mem, const uint32_t* xp, Put&& put) {
-    const uint32_t R = kb_nrec(C);
-    if (C.packed) {
-        int64_t cpu, mem;
-        uint32_t o = 0;
-        pod_request(f, cpu0, mem0, xc_cpu, xc_mem, o, cpu, mem);
-        if (C.packed == 2) {
-            put(8, blk / 2 + kb_pos64(sl), kp8_word(f, (uint32_t)cpu, mem, pair0));
-        } else {
-            put(4, blk + sl, kp_word(f, pair0));
-            put(8, (blk + KP_CM0) / 2 + kb_pos64(sl), kp_val(cpu, mem));
-        }
-    } else {
-        put(4, blk + sl, f);
-        put(4, blk + KB_CPU0 + sl, cpu0);
-        put(8, (blk + KB_MEM0) / 2 + kb_pos64(sl), (uint64_t)mem0);
-        put(4, blk + KB_PAIR0 + sl, pair0);
-        for (uint32_t k = 0; k < R; ++k) {
-            const int64_t o = kb_rec64(blk, k, sl);
-            put(8, o, (uint64_t)xc_cpu[k]);
-            put(8, o + 256, (uint64_t)xc_mem[k]);
-        }
-    }
-    if (C.packed == 2) {                       // u16 pairs; a daemonset pod has none (kp8_word)
-        for (uint32_t k = 0; k < C.nxp; ++k)
-            put(2, kb_xp(C, blk, k, sl), (f & ESC_PF_DAEMONSET) || xp[k] >= KP8_XP_NONE ? KP8_XP_NONE : xp[k]);
-    } else {
-        for (uint32_t k = 0; k < C.nxp; ++k) put(4, kb_xp(C, blk, k, sl), xp[k]);
-    }
-}
 
 // Device view of a pod shard.  Two sections, made at load (esc_load_pods; sums are
 // order-independent):
 //  - K: pods with at most 3 extra container records and at most 3 extra pairs, grouped by
-//    record signature into 256-pod tiles, each tile one contiguous block (kb, above);
+//    record signature into 256-pod tiles, each tile one contiguous block (kb: esc_kblock.h);
 //  - C: the others, in 64-pod tiles (1 per lane) in their own SoA arrays (flags .. pair0
 //    indexed from the C section's start), whose extra records are contiguous per tile
 //    (xc_base / xp_base into xc_cpu / xc_mem / xp).
@@ -729,6 +472,19 @@ struct CompactDev {
     uint32_t* err;
 };
 hipError_t launch_nodes_compact(const CompactDev& c, hipStream_t st);
+// esc_pods_grow: the K blocks moved to the re-cut classes' tile ranges (k_kb_regrow, one
+// workgroup per new tile; KbRegrowCls: esc_kblock.h).  Sizes in u32 words; every source and
+// destination block is checked against them and a violation sets bits of *err.
+struct KbRegrow {
+    const uint32_t* old_kb;
+    const uint32_t* tmpl;              // the classes' free tiles (KbRegrowCls::tmpl)
+    uint32_t* new_kb;
+    const KbRegrowCls* tab;
+    int64_t old_words, tmpl_words, new_words;
+    int32_t n_cls;
+    uint32_t* err;
+};
+hipError_t launch_kb_regrow(const KbRegrow& r, int64_t n_tiles, hipStream_t st);
 // The bounded waits of the decoupled look-backs (k_ord_split, k_memb_keys): HIP does not
 // promise dispatch order, so a chunk never waits unboundedly on one that was not dispatched.
 // A chunk that waited `spins` probes gives up: it publishes a FAILED status word (never an

@@ -3557,7 +3557,76 @@ __global__ __launch_bounds__(256) void k_run_move(CompactDev C) {
     for (int64_t k = lane; k < words; k += 64) C.refs_new[dst + k] = C.refs_old[src + k];
 }
 
+// ===================================================================== pod classes grown
+// esc_pods_grow (KbRegrow, esc_kernels.h).  One 256-thread workgroup per NEW K
+// tile: it finds its class in the staged table (a binary search over at most 72 ascending
+// ranges, wave-uniform loads) and
+// copies the tile's block, wt * 512 B, 16 B per lane and round, from the old array (a tile the
+// class had) or from the class's free tile among the templates (a tile it gained).  A block is a
+// multiple of 512 B and starts at one, so every access is 16-B aligned; wt is odd for some
+// classes, so a round's last lanes may have nothing to do.  The source is read once
+// (nontemporal loads), every round's loads are issued before its stores, and every offset is the
+// host's: no workgroup looks at another's.  A tile no class holds, or a block outside either
+// buffer, is reported and copies nothing.
+namespace {
+constexpr uint32_t RG_ERR_CLASS = 1u, RG_ERR_SRC = 2u, RG_ERR_DST = 4u;
+constexpr int RG_UNROLL = 4;           // 16-B loads in flight per lane: 16 KB per round, wt <= 40 in <= 2 rounds
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_kb_regrow(KbRegrow R) {
+    const int64_t t = blockIdx.x;
+    // the last class that starts at or before the tile (the ranges ascend): at most 7 dependent
+    // wave-uniform loads; the class's own range is checked below
+    int ci = 0;
+    for (int hi = R.n_cls; hi - ci > 1;) {
+        const int mid = (ci + hi) >> 1;
+        if (R.tab[mid].t0 <= t) ci = mid;
+        else hi = mid;
+    }
+    if (R.n_cls <= 0 || t < R.tab[ci].t0 || t >= R.tab[ci].t1) {
+        if (threadIdx.x == 0) rb_fail(R.err, RG_ERR_CLASS);
+        return;
+    }
+    const KbRegrowCls C = R.tab[ci];
+    const int64_t j = t - C.t0, words = (int64_t)C.wt * KB_UNIT;
+    const bool kept = j < C.old_tiles;
+    const int64_t src = kept ? C.old_kb0 + j * words : C.tmpl;
+    const int64_t src_words = kept ? R.old_words : R.tmpl_words;
+    const int64_t dst = C.new_kb0 + j * words;
+    if (src < 0 || (src & 3) || src + words > src_words) {
+        if (threadIdx.x == 0) rb_fail(R.err, RG_ERR_SRC);
+        return;
+    }
+    if (dst < 0 || (dst & 3) || dst + words > R.new_words) {
+        if (threadIdx.x == 0) rb_fail(R.err, RG_ERR_DST);
+        return;
+    }
+    const v4u32* __restrict__ s = reinterpret_cast<const v4u32*>((kept ? R.old_kb : R.tmpl) + src);
+    v4u32* __restrict__ d = reinterpret_cast<v4u32*>(R.new_kb + dst);
+    const int n16 = (int)(words / 4);                  // wt * 32: a multiple of 32, not of 64
+    for (int base = 0; base < n16; base += 256 * RG_UNROLL) {
+        v4u32 v[RG_UNROLL];
+#pragma unroll
+        for (int u = 0; u < RG_UNROLL; ++u) {
+            const int k = base + u * 256 + (int)threadIdx.x;
+            if (k < n16) v[u] = __builtin_nontemporal_load(s + k);
+        }
+#pragma unroll
+        for (int u = 0; u < RG_UNROLL; ++u) {
+            const int k = base + u * 256 + (int)threadIdx.x;
+            if (k < n16) d[k] = v[u];
+        }
+    }
+}
+
 // ===================================================================== launchers
+hipError_t launch_kb_regrow(const KbRegrow& r, int64_t n_tiles, hipStream_t st) {
+    if (n_tiles <= 0) return hipSuccess;
+    if (n_tiles > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_kb_regrow, dim3((unsigned)n_tiles), dim3(256), 0, st, r);
+    return hipGetLastError();
+}
+
 hipError_t launch_nodes_compact(const CompactDev& c, hipStream_t st) {
     static_assert(sizeof(PodRef) == 20, "k_run_move copies a PodRef as five words");
     if (c.n_new > 0) hipLaunchKernelGGL(k_node_gather, dim3((unsigned)((c.n_new + 255) / 256)), dim3(256), 0, st, c);

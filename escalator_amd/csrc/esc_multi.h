@@ -42,6 +42,7 @@ int32_t fail_hip(hipError_t e, const char* what);
 // check phases of esc_pods_upsert / esc_pods_bind (nothing applied)
 int32_t pods_upsert_check(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p);
 int32_t pods_bind_check(esc_ctx* c, const int64_t* ids, const uint32_t* pod_node, int64_t n);
+int32_t pods_grow_check(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p);   // esc_pods_grow's checks and plan
 int32_t nodes_relabel_check(esc_ctx* c, const int64_t* ids, const esc_node_soa* s);
 
 // ---- the multi-device context: every ABI call on it dispatches to these (esc_multi.hip)
@@ -59,6 +60,7 @@ int32_t multi_each(esc_ctx* c, int32_t (*fn)(esc_ctx*, int32_t), int32_t arg);  
 esc_ctx* multi_sub(const esc_ctx* c, int i);                                     // device i's context
 int32_t multi_k1_calibrate(esc_ctx* c, int32_t rounds);
 int32_t multi_pods_upsert(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p);
+int32_t multi_pods_grow(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p);
 int32_t multi_pods_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_pods_bind(esc_ctx* c, const int64_t* ids, const uint32_t* pod_node, int64_t n);
 int32_t multi_nodes_update(esc_ctx* c, const int64_t* ids, int64_t n, const uint32_t* flags, const int64_t* cpu,

@@ -349,12 +349,12 @@ int32_t multi_k1_calibrate(esc_ctx* c, int32_t rounds) {
 }
 
 // ---------------------------------------------------------------- informer events
-int32_t multi_pods_upsert(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) {
+// A pod event batch split by the devices' shards (owner_of_pod), ids made shard-local.
+static int32_t split_pod_batch(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, std::vector<PodBatch>& b) {
     if (!p || p->n_pods < 0 || (p->n_pods > 0 && (!ids || !p->flags || !p->cpu0 || !p->mem0 || !p->pair0)))
         return ESC_E_INVAL;
-    const int k = nsub(c);
     if (M(c).pod_lo.empty()) return ESC_E_STATE;
-    std::vector<PodBatch> b(k);
+    b.assign((size_t)nsub(c), PodBatch());
     int64_t oc = 0, op = 0;
     for (int64_t i = 0; i < p->n_pods; ++i) {
         const uint32_t f = p->flags[i], nc = pf_xctr(f), nx = pf_xpair(f);
@@ -373,6 +373,34 @@ int32_t multi_pods_upsert(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) 
         op += nx;
     }
     if (oc != p->n_xc || op != p->n_xp) return ESC_E_INVAL;
+    return ESC_OK;
+}
+
+// esc_pods_grow: every device's share is checked before any device grows (all or nothing up
+// to the first swap); a device whose share is empty only has its spare fraction restored.
+int32_t multi_pods_grow(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) {
+    const int k = nsub(c);
+    std::vector<PodBatch> b((size_t)k);
+    if (p && p->n_pods != 0) {
+        if (int32_t rc = split_pod_batch(c, ids, p, b)) return rc;
+    } else if (M(c).pod_lo.empty()) {
+        return ESC_E_STATE;
+    }
+    for (int s = 0; s < k; ++s) {
+        const esc_pod_soa v = b[s].view();
+        if (int32_t rc = pods_grow_check(M(c).subs[s], b[s].ids.data(), &v)) return rc;
+    }
+    for (int s = 0; s < k; ++s) {
+        const esc_pod_soa v = b[s].view();
+        if (int32_t rc = esc_pods_grow(M(c).subs[s], b[s].ids.data(), &v)) return rc;
+    }
+    return ESC_OK;
+}
+
+int32_t multi_pods_upsert(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) {
+    const int k = nsub(c);
+    std::vector<PodBatch> b;
+    if (int32_t rc = split_pod_batch(c, ids, p, b)) return rc;
     // every device's share checked before any is applied: all or nothing across devices
     for (int s = 0; s < k; ++s) {
         if (b[s].ids.empty()) continue;

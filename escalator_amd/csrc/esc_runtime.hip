@@ -203,35 +203,6 @@ int32_t occ_recount(esc_ctx* c) {
 
 namespace {
 
-// A kb_write_pod / kb_write_free put into the host copy of the K blocks.
-void put_kb(uint32_t* kb, int width, int64_t at, uint64_t v) {
-    if (width == 8) reinterpret_cast<int64_t*>(kb)[at] = (int64_t)v;
-    else if (width == 4) kb[at] = (uint32_t)v;
-    else reinterpret_cast<uint16_t*>(kb)[at] = (uint16_t)v;
-}
-
-// Spare C slots (esc_load_pods with esc_set_spare): room per slot, slots per 64-pod tile.
-constexpr int CS_SLOTS = 16, CS_XREG = 4, CS_XINIT = 2, CS_REC = CS_XREG + CS_XINIT + 1, CS_XP = 6;
-static_assert(CS_SLOTS * CS_REC <= 128 && CS_SLOTS * CS_XP <= 128, "a spare C tile stays on K1's C path");
-constexpr uint32_t CS_FLAGS = ESC_PF_DAEMONSET | ESC_PF_HAS_OVH | (uint32_t)CS_XREG << ESC_PF_XREG_SHIFT |
-                              (uint32_t)CS_XINIT << ESC_PF_XINIT_SHIFT | (uint32_t)CS_XP << ESC_PF_XPAIR_SHIFT;
-
-// K class of a pod, the one place that decides it: -1 for the C section (more
-// than 3 extra container records or more than 3 extra pairs); else the fold (kp_fold) either
-// packs the pod's effective request — class id = its pair count np | packed << 7, packed 2
-// for the packed small block and 1 for the packed block, a signature without records — or
-// leaves the pod its records in the plain class of its own signature.  xc_cpu / xc_mem: the
-// pod's own records (null when it has none).
-int pod_class_id(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
-                 const int64_t* xc_mem, uint32_t n_gp) {
-    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, np = pf_xpair(f);
-    if (xr + xi + ov > 3 || np > 3) return -1;
-    int64_t cpu, mem;
-    const uint32_t packed = kp_fold(f, cpu0, mem0, pair0, xc_cpu, xc_mem, n_gp, cpu, mem);
-    if (packed) return (int)(np | packed * POD_SIG_IDS);
-    return (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
-}
-
 // The exchange buffer (SUM across ranks, reduce-scattered to the owners): the pods' words
 // in owner-major rows, [world][own_cap][PW_K].
 int64_t xw_count(const esc_ctx* c) { return (int64_t)c->world * c->own_cap * PW_K; }
@@ -305,7 +276,9 @@ hipError_t enqueue_order(esc_ctx* c, hipStream_t st) {
                                c->d_ord, c->d_seg, st);
 }
 
-void release_work(esc_ctx* c) {
+}  // namespace
+
+void esc::release_work(esc_ctx* c) {
     dfree(c->d_k1seg); dfree(c->d_pod_part); dfree(c->d_wide_pod); dfree(c->d_trk_acc);
     dfree(c->d_k1_trace);
     dfree(c->d_ttrace);
@@ -324,6 +297,8 @@ void release_work(esc_ctx* c) {
     c->work_ready = false;
     drop_graphs(c);
 }
+
+namespace {
 
 void release_placement(esc_ctx* c) {
     dfree(c->d_refs); dfree(c->d_e_pair); dfree(c->d_nrun_off); dfree(c->d_nrun_len); dfree(c->d_occ); dfree(c->d_rm_off);
@@ -887,8 +862,10 @@ int32_t guarded(esc_ctx* c, uint32_t bit, F&& apply) {
     return rc;
 }
 
+}  // namespace
+
 // Grid geometry for the current snapshot.
-int32_t ensure_work(esc_ctx* c) {
+int32_t esc::ensure_work(esc_ctx* c) {
     if (c->work_ready) return ESC_OK;
     const int32_t G = c->gi.G;
     const int64_t S = pod_slots(c);
@@ -977,6 +954,8 @@ int32_t ensure_work(esc_ctx* c) {
     c->work_ready = true;
     return touch_refresh(c, plan);
 }
+
+namespace {
 
 // Enqueue one step for replica r on the context's stream, three launches in order:
 //   K1  the pod pass (LDS windows of pod slots; the exact paths when needed),
@@ -1453,7 +1432,7 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     const int64_t n_cs = c->spare_frac > 0 ? std::max<int64_t>(CS_SLOTS, (int64_t)std::ceil((double)n_c * c->spare_frac)) : 0;
     const int64_t c_real = (n_c + CTILE - 1) / CTILE, cs_tiles = (n_cs + CS_SLOTS - 1) / CS_SLOTS;
     const int64_t k_tiles = kt, c_tiles = c_real + cs_tiles;
-    const int64_t c0 = k_tiles * TILE, npad = c_tiles * CTILE;   // C arrays: the C section only
+    const int64_t npad = c_tiles * CTILE;                        // C arrays: the C section only
     // C record arrays; one element of padding (K1 clamps its unconditional C record loads)
     const int64_t nxc_dev = (int64_t)sc_c + cs_tiles * CS_SLOTS * CS_REC + 1, nxp_dev = (int64_t)sp_c + cs_tiles * CS_SLOTS * CS_XP + 1;
     if (nxc_dev >= (int64_t)0xFFFFFFFF || nxp_dev >= (int64_t)0xFFFFFFFF) return ESC_E_LIMIT;
@@ -1531,9 +1510,9 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
                              [&](int width, int64_t at, uint64_t v) { put_kb(hkb.data(), width, at, v); });
             } else {
                 if (ic % CTILE == 0) { xc_base[ic / CTILE] = (uint32_t)oc; xp_base[ic / CTILE] = (uint32_t)op; }
-                const int64_t d = ic++;                   // C-array index (slot c0 + d)
+                const int64_t d = ic++;                   // C-array index (slot k_tiles * TILE + d)
                 pod_cls[i] = -1;
-                pod_pos[i] = c0 + d;
+                pod_pos[i] = d;
                 for (uint32_t j = 0; j < nc; ++j) { hxc[oc + j] = p->xc_cpu[rc + j]; hxm[oc + j] = p->xc_mem[rc + j]; }
                 for (uint32_t j = 0; j < nx; ++j) hxp[op + j] = p->xp_pair[rp + j];
                 oc += nc;
@@ -1623,6 +1602,7 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     for (int64_t d = 0; d < npad; ++d)
         if (!(hf[d] & ESC_PF_DAEMONSET) || d < n_c) c->h_cused[d] = pf_xctr(hf[d]) | pf_xpair(hf[d]) << 16;
     c->live_pods = n;
+    c->live_c_pods = n_c;
     c->live_xc = (int64_t)sc_c;                       // records K1 streams: the C pods' and the plain K pods'
     c->live_xp = p->n_xp;
     c->live_pk_pods = c->live_p8_pods = c->live_p8_xp = 0;
@@ -2646,7 +2626,7 @@ void remove_pod(esc_ctx* c, int64_t id, Patches& P) {
     const int32_t ci = c->pod_cls[id];
     if (ci == -2) return;
     if (ci == -1) {
-        const int64_t d = c->pod_pos[id] - c->k_tiles * TILE;    // C-array index
+        const int64_t d = c->pod_pos[id];                        // C-array index
         uint32_t& f = c->h_cflags[d];
         c->live_xc -= c->h_cused[d] & 0xFFFF;
         c->live_xp -= c->h_cused[d] >> 16;
@@ -2654,6 +2634,7 @@ void remove_pod(esc_ctx* c, int64_t id, Patches& P) {
         f |= ESC_PF_DAEMONSET;
         P.add(PT_FLAGS, d, f);
         c->c_free.push_back(d);                           // its room (counts) stays: reusable
+        --c->live_c_pods;
     } else {
         const PodClass& k = c->h_cls[ci];
         const int64_t q = c->pod_pos[id];
@@ -2674,7 +2655,7 @@ void remove_pod(esc_ctx* c, int64_t id, Patches& P) {
 int64_t pod_slot(const esc_ctx* c, int64_t id) {
     const int32_t ci = c->pod_cls[id];
     const int64_t d = c->pod_pos[id];
-    return ci >= 0 ? (c->h_cls[ci].t0 + d / TILE) * TILE + d % TILE : d;
+    return ci >= 0 ? (c->h_cls[ci].t0 + d / TILE) * TILE + d % TILE : c->k_tiles * TILE + d;
 }
 
 // The PodRefs now at run positions pos (on nodes node) added to (+1) or removed from (-1)
@@ -3073,24 +3054,17 @@ struct UpsertPlan {
     std::vector<int64_t> cslot;
 };
 
-// Does C slot room `cf` (counts of a slot's flags) hold a pod with flags f?  Its records
-// and pairs take the slot's first positions of each kind, the rest stay neutral.
-bool c_room(uint32_t cf, uint32_t f) {
-    return pf_xreg(f) <= pf_xreg(cf) && pf_xinit(f) <= pf_xinit(cf) && (!(f & ESC_PF_HAS_OVH) || (cf & ESC_PF_HAS_OVH)) &&
-           pf_xpair(f) <= pf_xpair(cf);
-}
-
 // Writes pod i of the batch into C slot d (its room: the slot's flags' counts; the pod's
 // records and pairs first of each kind, the rest neutral — 0 for added records, absent keys
 // for init containers, NONE for pairs).  True when K1's touched columns grew.
 bool upsert_c(esc_ctx* c, int64_t id, int64_t d, const esc_pod_soa* p, int64_t i, int64_t rof, int64_t pof, Patches& P) {
-    const int64_t c0 = c->k_tiles * TILE;
-    if (!(c->pod_cls[id] == -1 && c->pod_pos[id] - c0 == d)) {
+    if (!(c->pod_cls[id] == -1 && c->pod_pos[id] == d)) {
         remove_pod(c, id, P);
         auto it = std::find(c->c_free.begin(), c->c_free.end(), d);
         if (it != c->c_free.end()) c->c_free.erase(it);
         c->pod_cls[id] = -1;
-        c->pod_pos[id] = c0 + d;
+        c->pod_pos[id] = d;
+        ++c->live_c_pods;
     } else {
         --c->live_pods;                                   // re-added below
         c->live_xc -= c->h_cused[d] & 0xFFFF;
@@ -3131,43 +3105,25 @@ int32_t upsert_plan(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, Upsert
     if (!c->pods_loaded) return ESC_E_STATE;
     const int64_t n = p->n_pods;
     // validate the batch and that every pod fits in place (all or nothing)
-    std::vector<int64_t> need(c->h_cls.size(), 0), rof(n), pof(n), cslot(n, -1);
+    BatchShape sh;
+    if (int32_t rc = batch_shape(c, ids, p, sh)) return rc;
+    std::vector<int64_t> need(c->h_cls.size(), 0), cslot(n, -1);
     std::vector<int32_t> tgt(n);
     std::vector<char> taken(c->c_free.size(), 0);          // free C slots this batch takes
-    const int64_t c0 = c->k_tiles * TILE;
-    uint64_t sc = 0, sp = 0;
-    std::vector<int64_t> seen(ids, ids + n);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return ESC_E_INVAL;   // one event per id
     for (int64_t i = 0; i < n; ++i) {
-        if (ids[i] < 0 || ids[i] >= ((int64_t)1 << 31)) return ESC_E_INVAL;
-        const uint32_t f = p->flags[i], nx = pf_xpair(f), nc = pf_xctr(f);
-        uint32_t last = p->pair0[i];
-        if (last == NONE ? nx != 0 : last >= ESC_PAIR_LIMIT) return ESC_E_INVAL;
-        if (sp + nx > (uint64_t)p->n_xp || sc + nc > (uint64_t)p->n_xc) return ESC_E_INVAL;
-        for (uint32_t k = 0; k < nx; ++k) {
-            const uint32_t q = p->xp_pair[sp + k];
-            if (q >= ESC_PAIR_LIMIT || q <= last) return ESC_E_INVAL;
-            last = q;
-        }
-        rof[i] = (int64_t)sc;
-        pof[i] = (int64_t)sp;
-        sc += nc;
-        sp += nx;
-        const int sid = pod_class_id(f, p->cpu0[i], p->mem0[i], p->pair0[i], nc ? p->xc_cpu + sc - nc : nullptr,
-                                     nc ? p->xc_mem + sc - nc : nullptr, c->gi.n_gp);
+        const uint32_t f = p->flags[i];
+        const int sid = sh.sid[i];
         int ci = sid < 0 ? -1 : c->h_cls_of[sid];
         const int64_t id = ids[i];
-        const bool known = id < (int64_t)c->pod_cls.size();
-        if (ci >= 0 && !(known && c->pod_cls[id] == ci)) {
+        if (ci >= 0 && k_needs_pos(c, id, ci)) {
             if (need[ci] < (int64_t)c->cls_free[ci].size()) ++need[ci];
             else ci = -1;                                  // its class is full: a C slot
         }
         tgt[i] = ci;
         if (ci >= 0) continue;
         // a C slot: its own (when it has room), else a free one with room
-        if (known && c->pod_cls[id] == -1 && c_room(c->h_cflags[c->pod_pos[id] - c0], f)) {
-            cslot[i] = c->pod_pos[id] - c0;
+        if (c_keeps_slot(c, id, f)) {
+            cslot[i] = c->pod_pos[id];
             continue;
         }
         for (int64_t k = (int64_t)c->c_free.size() - 1; k >= 0 && cslot[i] < 0; --k)
@@ -3175,12 +3131,12 @@ int32_t upsert_plan(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, Upsert
                 taken[k] = 1;
                 cslot[i] = c->c_free[k];
             }
-        if (cslot[i] < 0) {                                // no room in place: reload
+        if (cslot[i] < 0) {                                // no room in place: esc_pods_grow, or a reload
             return ESC_E_LIMIT;
         }
     }
-    u.rof.swap(rof);
-    u.pof.swap(pof);
+    u.rof.swap(sh.rof);
+    u.pof.swap(sh.pof);
     u.tgt.swap(tgt);
     u.cslot.swap(cslot);
     return ESC_OK;
@@ -3280,6 +3236,37 @@ int32_t bind_check(esc_ctx* c, const int64_t* ids, const uint32_t* pod_node, int
 }  // namespace
 
 namespace esc {
+// The checks of a pod event batch (one event per id, ids in range, pair lists ascending and
+// unique, the record and pair counts inside the batch's arrays) and every pod's class id.
+int32_t batch_shape(const esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, BatchShape& b) {
+    const int64_t n = p->n_pods;
+    b.rof.assign((size_t)n, 0);
+    b.pof.assign((size_t)n, 0);
+    b.sid.assign((size_t)n, -1);
+    uint64_t sc = 0, sp = 0;
+    std::vector<int64_t> seen(ids, ids + n);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return ESC_E_INVAL;   // one event per id
+    for (int64_t i = 0; i < n; ++i) {
+        if (ids[i] < 0 || ids[i] >= ((int64_t)1 << 31)) return ESC_E_INVAL;
+        const uint32_t f = p->flags[i], nx = pf_xpair(f), nc = pf_xctr(f);
+        uint32_t last = p->pair0[i];
+        if (last == NONE ? nx != 0 : last >= ESC_PAIR_LIMIT) return ESC_E_INVAL;
+        if (sp + nx > (uint64_t)p->n_xp || sc + nc > (uint64_t)p->n_xc) return ESC_E_INVAL;
+        for (uint32_t k = 0; k < nx; ++k) {
+            const uint32_t q = p->xp_pair[sp + k];
+            if (q >= ESC_PAIR_LIMIT || q <= last) return ESC_E_INVAL;
+            last = q;
+        }
+        b.rof[i] = (int64_t)sc;
+        b.pof[i] = (int64_t)sp;
+        b.sid[i] = (int16_t)pod_class_id(f, p->cpu0[i], p->mem0[i], p->pair0[i], nc ? p->xc_cpu + sc : nullptr,
+                                         nc ? p->xc_mem + sc : nullptr, c->gi.n_gp);
+        sc += nc;
+        sp += nx;
+    }
+    return ESC_OK;
+}
 int32_t pods_upsert_check(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) {
     UpsertPlan u;
     return upsert_plan(c, ids, p, u);

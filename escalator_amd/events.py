@@ -10,7 +10,10 @@ node call that answers ``ESC_E_LIMIT`` is first answered by ``nodes_rebuild`` (t
 re-derived on the device, no pod reloaded) and retried once.  With ``compact=True`` a
 ``nodes_add`` that lacks free table slots, and a ``pods_bind`` into a full run, are answered by
 ``nodes_compact`` (the live nodes renumbered into a fresh table on the device, the runs re-cut)
-and retried once; the queue's index maps follow the returned map.
+and retried once; the queue's index maps follow the returned map.  With ``pod_grow=True`` a
+``pods_upsert`` that answers ``ESC_E_LIMIT`` (more pods than the load left room for) is answered
+by one ``pods_grow`` with the same ids and packed batch (the pod classes grown on the device, no
+pod reloaded, every id kept) and one retry; a second limit reloads.
 
 It holds the current objects (plain-dict records, escalator_amd/objects.py) — the truth a
 reload is built from — and, beside them, what the device last saw of each.  Ingest
@@ -70,7 +73,7 @@ def _status(n: dict):
 
 
 class EventQueue:
-    def __init__(self, spare: float = 0.5, rebuild: bool = False, compact: bool = False):
+    def __init__(self, spare: float = 0.5, rebuild: bool = False, compact: bool = False, pod_grow: bool = False):
         self.spare = float(spare)
         self.compact = bool(compact)               # answer a lack of table slots / a full run with nodes_compact
         self.rebuild = bool(rebuild) or self.compact   # answer a node-side ESC_E_LIMIT with nodes_rebuild first
@@ -78,6 +81,9 @@ class EventQueue:
         self.rebuild_causes: list[str] = []        # the call that answered ESC_E_LIMIT, or "audit:<check>"
         self.compactions = 0
         self.compact_causes: list[str] = []        # the call that answered ESC_E_LIMIT
+        self.pod_grow = bool(pod_grow)             # answer a full pod class / C section with pods_grow
+        self.pod_grows = 0
+        self.pod_grow_causes: list[str] = []       # the call that answered ESC_E_LIMIT
         self.pods: dict[str, dict] = {}            # the object store: key -> pod, name -> node
         self.nodes: dict[str, dict] = {}           # (insertion order = arrival order)
         self._dev_pods: dict[str, dict] = {}       # the records the device holds, as last flushed
@@ -310,8 +316,17 @@ class EventQueue:
             pid[k] = self._take_id()
         if upsert:
             packed, _ = ctx.pack([self.pods[k] for k in upsert], [])
-            self._call("pods_upsert", len(upsert), ctx.pods_upsert, np.array([pid[k] for k in upsert], np.int64),
-                       packed)
+            ids = np.array([pid[k] for k in upsert], np.int64)
+            try:
+                self._call("pods_upsert", len(upsert), ctx.pods_upsert, ids, packed)
+            except _Reload:
+                if not self.pod_grow:
+                    raise
+                # a full class or C section: grown on the device for this batch, then one retry
+                self._call("pods_upsert", 0, ctx.pods_grow, ids, packed)
+                self.pod_grows += 1
+                self.pod_grow_causes.append("pods_upsert")
+                self._call("pods_upsert", len(upsert), ctx.pods_upsert, ids, packed)
         bind = list(born)
         seen = set(born)
         for k in changed:

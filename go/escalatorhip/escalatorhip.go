@@ -690,6 +690,36 @@ func (x *Context) PodsUpsert(ids []int64, pods []*v1.Pod) error {
 	})
 }
 
+// PodsGrow grows the pod classes on the device (esc_pods_grow) so that PodsUpsert(ids, pods)
+// made right after it cannot answer ErrReload: the answer to PodsUpsert's ErrReload when more
+// pods arrived than the load left room for.  No pod is reloaded and every id, the placement
+// and the node side stay.  Without pods it only restores the spare fraction over the live
+// counts.  ErrReload when a pod of the batch fits no spare C slot.
+func (x *Context) PodsGrow(ids []int64, pods []*v1.Pod) error {
+	if len(ids) != len(pods) {
+		return fmt.Errorf("escalatorhip: %d ids for %d pods", len(ids), len(pods))
+	}
+	if len(ids) == 0 {
+		return rcErr("esc_pods_grow", C.esc_pods_grow(x.c, nil, nil))
+	}
+	return x.pack(pods, nil, nil, false, func(ps *C.esc_pod_soa, _ *C.esc_node_soa) error {
+		rc := C.esc_pods_grow(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), ps)
+		if rc == C.ESC_E_LIMIT {
+			return ErrReload
+		}
+		return rcErr("esc_pods_grow", rc)
+	})
+}
+
+// PodsRoom returns the K positions in all, the free ones, the free C slots and, per class id,
+// the free positions (-1: the id has no class) (esc_pods_room).
+func (x *Context) PodsRoom() (kCapacity, kFree, cFree int64, perClass []int64, err error) {
+	var a, b, d C.int64_t
+	perClass = make([]int64, 384)
+	err = rcErr("esc_pods_room", C.esc_pods_room(x.c, &a, &b, &d, (*C.int64_t)(unsafe.Pointer(ptr(perClass)))))
+	return int64(a), int64(b), int64(d), perClass, err
+}
+
 // PodsDelete removes pods by snapshot index.
 func (x *Context) PodsDelete(ids []int64) error {
 	return rcErr("esc_pods_delete", C.esc_pods_delete(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), C.int64_t(len(ids))))

@@ -505,6 +505,42 @@ int32_t esc_set_spare(esc_ctx* ctx, double fraction);       /* spare room: per K
                                                                 node slots / entries / K5 regions (esc_load_nodes) */
 int32_t esc_pods_upsert(esc_ctx* ctx, const int64_t* ids, const esc_pod_soa* pods);
 int32_t esc_pods_delete(esc_ctx* ctx, const int64_t* ids, int64_t n);
+/* More pods than the load left room for.  esc_pods_grow re-lays the pod side on the device so
+ * that esc_pods_upsert(ctx, ids, pods) made right after it cannot answer ESC_E_LIMIT; with
+ * pods NULL or empty it only restores the spare fraction over the live counts.  No pod is
+ * re-uploaded: classes are contiguous ranges of 256-pod tile blocks and a tile's inside does
+ * not depend on where it lies, so whole blocks move device to device.  Classes never shrink
+ * and no resident pod changes its class or its position inside it.  The rule:
+ *   K classes.  The batch is classified as esc_pods_upsert does (a pod already in its class
+ *   needs no new position; departures are not credited).  For class i with live_i = capacity -
+ *   free positions and arr_i arrivals that need a new position,
+ *     want_i = live_i + arr_i + s(live_i + arr_i),  s(x) = f > 0 ? max(1, floor(x * f)) : 0,
+ *     tiles_i = max(old tiles_i, ceil(want_i / 256))       (f: esc_set_spare's fraction).
+ *   A class the batch needs and the context lacks (possible only when it was loaded with f = 0)
+ *   is appended behind the existing ones, in ascending class id.  Tile ranges are re-cut in
+ *   class-index order.
+ *   C section.  arr_c = batch pods with > 3 records or > 3 extra pairs that cannot stay in
+ *   their own slot; one that a spare slot cannot hold makes the call ESC_E_LIMIT (that pod
+ *   needs a reload).  With free_cs = free C slots of at least a spare slot's room and
+ *     want_cs = arr_c + (f > 0 ? max(16, ceil((pods in C slots + arr_c) * f)) : 0),
+ *   ceil(max(0, want_cs - free_cs) / 16) spare C tiles of 16 slots are appended.  Pods parked
+ *   in C slots because their class was once full stay there.
+ * Kept: pod ids, classes, positions, every pod's bytes, the placement and the occupancy
+ * words, the node side, the age index, esc_set_state, the tracker, esc_stream_bytes, the K1
+ * calibration when the grid did not change.  Invalidated, as after esc_load_pods: captured
+ * graphs, the last decision's records, selections and esc_try_remove results.
+ * All or nothing up to the swap of the new arrays: ESC_E_INVAL (a batch esc_pods_upsert would
+ * call invalid), ESC_E_LIMIT (above, or offsets past 32 bits), ESC_E_NOMEM / ESC_E_HIP leave
+ * the snapshot as it was; a failure after the swap (another replica, the work set) leaves the
+ * context stale until esc_load_pods, as a failed pod event does.  ESC_E_STATE before
+ * esc_load_pods or on a stale context.  Multi-device: every device's share of the batch is
+ * checked before any device grows; the ranks of a sharded job each grow their own shard.
+ * esc_pods_room reports (any pointer may be NULL) the K positions in all, the free ones, the
+ * free C slots and, per class id (384 of them), the free positions, -1 where the id has no
+ * class; multi-device: summed over the devices.                                        */
+int32_t esc_pods_grow(esc_ctx* ctx, const int64_t* ids, const esc_pod_soa* pods);
+int32_t esc_pods_room(const esc_ctx* ctx, int64_t* k_capacity, int64_t* k_free, int64_t* c_free,
+                      int64_t* per_class /* [384] or NULL */);
 int32_t esc_nodes_update(esc_ctx* ctx, const int64_t* ids, int64_t n, const uint32_t* flags,
                          const int64_t* cpu_m, const int64_t* mem_b);
 /* Node additions and deletions (the node informer's Add / Delete, pkg/k8s/cache.go:37-56)
