@@ -292,9 +292,9 @@ class Context:
 
     def pods_room(self) -> dict:
         """esc_pods_room: ``k_capacity`` (K positions in all), ``k_free``, ``c_free`` (free C
-        slots) and ``per_class`` (int64[384] by class id: free positions, -1 without a class)."""
+        slots) and ``per_class`` (int64[512] by class id: free positions, -1 without a class)."""
         a, b, d = C.c_int64(), C.c_int64(), C.c_int64()
-        per = np.zeros(384, np.int64)
+        per = np.zeros(512, np.int64)
         L.check(self.lib.esc_pods_room(self.handle, C.byref(a), C.byref(b), C.byref(d),
                                        per.ctypes.data_as(C.POINTER(C.c_int64))), "esc_pods_room")
         return {"k_capacity": a.value, "k_free": b.value, "c_free": d.value, "per_class": per}

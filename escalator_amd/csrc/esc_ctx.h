@@ -305,6 +305,7 @@ struct esc_ctx {
     int64_t live_c_pods = 0;                    // of them in C slots (their own, or parked there by a full class)
     int64_t live_pk_pods = 0;                   // of them in packed K classes (either size; no records there)
     int64_t live_p8_pods = 0, live_p8_xp = 0;   // of them in packed small K classes, their extra pairs
+    int64_t live_inert_pods = 0, live_inert_xp = 0;   // of those in inert classes (K1 streams none of them)
     int64_t c_tiles_loaded = 0;                 // C tiles of loaded pods (the spare C tiles excluded)
     // node state mirrors for esc_nodes_update
     std::vector<uint32_t> h_nflags;

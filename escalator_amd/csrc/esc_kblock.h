@@ -25,9 +25,12 @@ struct PodClass {
     int64_t w0;                // K1 work weight of the tiles before t0
     uint32_t xreg, xinit, ovh, nxp;
     uint32_t kind;             // selects K1's pipeline: plain (xreg + xinit + ovh) * 4 + nxp, packed 16 + nxp,
-                               // packed small 20 + nxp (a packed class has no records: kp_fold)
-    uint32_t wt;               // work weight of one tile: its 16-B loads per lane (= block KB)
-    uint32_t packed;           // 0 plain, 1 packed (12 B / pod), 2 packed small (8 B / pod): kp_*, kp8_* below
+                               // packed small 20 + nxp (a packed class has no records: kp_fold); inert
+                               // K_KIND_INERT + nxp, which no pipeline takes (kb_inert below)
+    uint32_t wt;               // size of one tile's block in KB_UNIT words: its 16-B loads per lane, and its
+                               // K1 work weight unless the class is inert (kb_k1_wt)
+    uint32_t packed;           // the tile format: 0 plain, 1 packed (12 B / pod), 2 packed small (8 B / pod):
+                               // kp_*, kp8_* below (an inert class: 2)
     uint32_t pad;
 };
 // weight of a K tile with R records and NXP extra pairs per pod: its block size in half-KB
@@ -42,7 +45,16 @@ constexpr uint32_t k_kind(uint32_t R, uint32_t NXP, uint32_t packed) {
 constexpr uint32_t K_TILE_WEIGHT_MIN = 4;   // the lightest tile (packed small, no records or pairs)
 constexpr int64_t KB_UNIT = 128;            // u32 words per weight unit
 constexpr int POD_SIG_IDS = 128;     // signatures with <= 3 extra records and <= 3 extra pairs
-constexpr int POD_CLASS_IDS = 384;   // class id = signature | packed << 7
+constexpr int POD_CLASS_IDS = 512;   // class id = signature | packed << 7, an inert class's signature | 3 << 7
+// Inert classes: packed small tiles of pods no group can ever count (pod_inert,
+// esc_pod_layout.h).  Every per-class mechanism treats them as the packed small class of the
+// same extra-pair count; they weigh nothing in K1's plan, so no workgroup's share holds one of
+// their tiles, and their kind is one no K1 pipeline is instantiated for.
+constexpr int POD_INERT_ID0 = 3 * POD_SIG_IDS;
+constexpr uint32_t K_KIND_INERT = 24;
+ESC_KB_HD bool kb_inert(const PodClass& C) { return C.kind >= K_KIND_INERT; }
+// K1 work weight of one tile of the class: its block size, or 0 when K1 never streams it
+ESC_KB_HD uint32_t kb_k1_wt(const PodClass& C) { return kb_inert(C) ? 0u : C.wt; }
 constexpr int K1_SEGS = 4;           // class runs per K1 workgroup in the work plan (at most)
 
 // K blocks (tile-major K section).  Tile t of a class is ONE contiguous block of wt KB

@@ -3559,7 +3559,7 @@ __global__ __launch_bounds__(256) void k_run_move(CompactDev C) {
 
 // ===================================================================== pod classes grown
 // esc_pods_grow (KbRegrow, esc_kernels.h).  One 256-thread workgroup per NEW K
-// tile: it finds its class in the staged table (a binary search over at most 72 ascending
+// tile: it finds its class in the staged table (a binary search over at most 76 ascending
 // ranges, wave-uniform loads) and
 // copies the tile's block, wt * 512 B, 16 B per lane and round, from the old array (a tile the
 // class had) or from the class's free tile among the templates (a tile it gained).  A block is a

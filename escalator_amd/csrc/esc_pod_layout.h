@@ -35,18 +35,35 @@ static_assert(CS_SLOTS * CS_REC <= 128 && CS_SLOTS * CS_XP <= 128, "a spare C ti
 constexpr uint32_t CS_FLAGS = ESC_PF_DAEMONSET | ESC_PF_HAS_OVH | (uint32_t)CS_XREG << ESC_PF_XREG_SHIFT |
                               (uint32_t)CS_XINIT << ESC_PF_XINIT_SHIFT | (uint32_t)CS_XP << ESC_PF_XPAIR_SHIFT;
 
+// Can no group ever count the pod, whatever the groups' state?  A daemonset pod is excluded
+// by both filters (node_group.go:221, :259); a pod that blocks the default filter (static, a
+// selector, a blocking affinity) joins only the slots of its pairs, so it is inert when none
+// of them is a group pair (< n_gp).  A pod that does not block the default filter joins the
+// default slot and is never inert.  (escalator_amd/layout.py inert_mask restates it.)
+inline bool pod_inert(uint32_t f, uint32_t pair0, const uint32_t* xp, uint32_t n_gp) {
+    if (f & ESC_PF_DAEMONSET) return true;
+    if (!(f & (ESC_PF_STATIC | ESC_PF_HAS_SEL | ESC_PF_AFF_BLOCK))) return false;
+    if (pair0 < n_gp) return false;
+    for (uint32_t k = 0, np = pf_xpair(f); k < np; ++k)
+        if (xp[k] < n_gp) return false;
+    return true;
+}
+
 // K class of a pod, the one place that decides it: -1 for the C section (more
 // than 3 extra container records or more than 3 extra pairs); else the fold (kp_fold) either
 // packs the pod's effective request — class id = its pair count np | packed << 7, packed 2
 // for the packed small block and 1 for the packed block, a signature without records — or
 // leaves the pod its records in the plain class of its own signature.  xc_cpu / xc_mem: the
-// pod's own records (null when it has none).
+// pod's own records (null when it has none).  xp: its extra pairs (null when it has none).  A
+// pod of the packed small block that is inert (pod_inert) takes the inert class of its pair
+// count instead, id np | 3 << 7: the same tile, kept out of K1's stream.
 inline int pod_class_id(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
-                        const int64_t* xc_mem, uint32_t n_gp) {
+                        const int64_t* xc_mem, const uint32_t* xp, uint32_t n_gp) {
     const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, np = pf_xpair(f);
     if (xr + xi + ov > 3 || np > 3) return -1;
     int64_t cpu, mem;
     const uint32_t packed = kp_fold(f, cpu0, mem0, pair0, xc_cpu, xc_mem, n_gp, cpu, mem);
+    if (packed == 2 && pod_inert(f, pair0, xp, n_gp)) return (int)(np | POD_INERT_ID0);
     if (packed) return (int)(np | packed * POD_SIG_IDS);
     return (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
 }
@@ -72,15 +89,31 @@ inline PodClass pod_class_of_id(int id) {
     k.ovh = (uint32_t)((sig / 4) % 2);
     k.xinit = (uint32_t)((sig / 8) % 4);
     k.xreg = (uint32_t)(sig / 32);
-    k.packed = (uint32_t)(id / POD_SIG_IDS);
+    const bool inert = id >= POD_INERT_ID0;               // the packed small tile, a kind of its own
+    k.packed = inert ? 2u : (uint32_t)(id / POD_SIG_IDS);
     const uint32_t R = k.xreg + k.xinit + k.ovh;
-    k.kind = k_kind(R, k.nxp, k.packed);
+    k.kind = inert ? K_KIND_INERT + k.nxp : k_kind(R, k.nxp, k.packed);
     k.wt = k_tile_weight(R, k.nxp, k.packed);
     return k;
 }
 
+// Class ids in the load's table order: packed small, packed, plain, then the inert classes, so
+// that K1 streams the packed classes first and the inert ones move no other class's range.
+inline int pod_class_order(int ord) {
+    const int blk = ord / POD_SIG_IDS;
+    return (blk < 3 ? 2 - blk : 3) * POD_SIG_IDS + ord % POD_SIG_IDS;
+}
+// Can the K layout hold class id at all?  Plain: every signature of at most 3 records; the
+// packed and inert classes: the 4 without records.
+inline bool pod_class_holdable(int id) {
+    const int sig = id % POD_SIG_IDS;
+    return id < POD_SIG_IDS ? (sig / 32) + ((sig / 8) % 4) + ((sig / 4) % 2) <= 3 : sig < 4;
+}
+
 // Cuts the classes' tile ranges from their tile counts, in class-index order: t0 / t1, kb0 and
 // w0 ascend.  Returns the K section's tiles; kb_words / weight: its block words and work weight.
+// An inert class has real tiles and block words and no weight (kb_k1_wt): K1's walks split the
+// weight, so none of them reaches its tiles.
 inline int64_t cut_pod_classes(std::vector<PodClass>& cls, const std::vector<int64_t>& tiles, int64_t& kb_words,
                                int64_t& weight) {
     int64_t kt = 0;
@@ -92,7 +125,7 @@ inline int64_t cut_pod_classes(std::vector<PodClass>& cls, const std::vector<int
         k.kb0 = kb_words;
         k.w0 = weight;
         kt += tiles[i];
-        weight += tiles[i] * (int64_t)k.wt;
+        weight += tiles[i] * (int64_t)kb_k1_wt(k);
         kb_words += tiles[i] * (int64_t)k.wt * KB_UNIT;
     }
     return kt;

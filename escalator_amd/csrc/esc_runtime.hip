@@ -659,8 +659,8 @@ std::vector<int64_t> plan_k1(const std::vector<PodClass>& cls, int64_t W, int64_
     cut[nblk] = W;
     std::vector<int> big, small;
     for (int i = 0; i < (int)cls.size(); ++i) {
-        const int64_t w = (cls[i].t1 - cls[i].t0) * (int64_t)cls[i].wt;
-        if (w == 0) continue;
+        const int64_t w = (cls[i].t1 - cls[i].t0) * (int64_t)kb_k1_wt(cls[i]);
+        if (w == 0) continue;                              // no tiles, or an inert class: in no share
         (w * nblk < W ? small : big).push_back(i);
     }
     std::sort(small.begin(), small.end(), [&](int a, int b) {
@@ -829,7 +829,7 @@ bool touch_mark_row(const esc_ctx* c, uint32_t* row, uint32_t f, uint32_t pair0,
 // Marks the columns a pod written into K slot q of class ci adds to (esc_pods_upsert);
 // true when its workgroup did not touch one of them yet.
 bool touch_mark(esc_ctx* c, int32_t ci, int64_t q, uint32_t f, uint32_t pair0, const uint32_t* xp) {
-    if (!c->touch_on || (f & ESC_PF_DAEMONSET)) return false;
+    if (!c->touch_on || (f & ESC_PF_DAEMONSET) || kb_inert(c->h_cls[ci])) return false;   // (inert: in no share)
     const int64_t t = c->h_cls[ci].t0 + q / TILE;
     auto it = std::upper_bound(c->h_tile_wg.begin(), c->h_tile_wg.end(), std::array<int64_t, 3>{t, INT64_MAX, INT64_MAX});
     if (it == c->h_tile_wg.begin() || t >= (it - 1)->at(1)) return false;   // a tile no workgroup streams (none)
@@ -873,6 +873,11 @@ int32_t esc::ensure_work(esc_ctx* c) {
     const int lds = (gw + FC_COL - 1) / FC_COL * FC_COL * 16;   // K1's two LDS halves, whole columns each
     const int per_cu = std::max(1, std::min(4, LDS_BYTES / std::max(lds, 1)));   // 2048 threads per CU
     int64_t nblk = c->cu_count * per_cu;
+    // the classes and tiles K1 streams: an inert class's tiles are in no share, so they ask for
+    // no workgroup (the grid is that of the same snapshot without its inert pods)
+    int64_t k_streamed = 0, n_streamed = 0;
+    for (const PodClass& k : c->h_cls)
+        if (!kb_inert(k)) { k_streamed += k.t1 - k.t0; ++n_streamed; }
     // every workgroup takes 1/nblk of the K tiles' weight + ceil(c_tiles/nblk) C tiles;
     // keep that within PODS_PER_BLOCK_MAX (exactness of the packed LDS partials)
     // A deliberately loose pre-bound (a share counted as LOOSE quarter shares, each with its
@@ -882,17 +887,17 @@ int32_t esc::ensure_work(esc_ctx* c) {
     auto block_pods = [&](int64_t b) {
         // a weight share holds at most share / (lightest tile weight) + one partial tile per class
         const int64_t nch = b * LOOSE;
-        return LOOSE * ((c->k_weight + nch - 1) / nch / K_TILE_WEIGHT_MIN + c->n_cls + 1) * TILE +
+        return LOOSE * ((c->k_weight + nch - 1) / nch / K_TILE_WEIGHT_MIN + n_streamed + 1) * TILE +
                ((c->c_tiles + b - 1) / b) * CTILE;
     };
     while (block_pods(nblk) > PODS_PER_BLOCK_MAX) nblk *= 2;
-    nblk = std::min<int64_t>(nblk, std::max(c->k_tiles, c->c_tiles));
+    nblk = std::min<int64_t>(nblk, std::max(k_streamed, c->c_tiles));
     std::vector<int64_t> plan;
     for (;;) {            // the plan's own per-workgroup pod counts must keep the LDS words exact
         if ((int64_t)c->k1_share.size() != nblk) c->k1_share.clear();
         plan = plan_k1(c->h_cls, c->k_weight, std::max<int64_t>(nblk, 1), c->k1_share);
         if (plan.empty()) break;
-        if (plan_worst(c, plan, nblk) <= PODS_PER_BLOCK_MAX || nblk >= std::max(c->k_tiles, c->c_tiles)) break;
+        if (plan_worst(c, plan, nblk) <= PODS_PER_BLOCK_MAX || nblk >= std::max(k_streamed, c->c_tiles)) break;
         nblk *= 2;
     }
     c->nblk = (int)nblk;
@@ -1349,7 +1354,8 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     // changes no result.  Padding pods carry ESC_PF_DAEMONSET, padding records are 0 and
     // padding pairs NONE.  class id = record signature | packed << 7 (pod_class_id: a packed
     // pod's records are folded into its request, so its signature has none; the packed
-    // classes are listed first so that K1 streams them first)
+    // classes are listed first so that K1 streams them first; the inert classes, which it never
+    // streams, last)
     hvec<int16_t> pid(n);
     std::vector<std::vector<int64_t>> ch_cnt(TT, std::vector<int64_t>(POD_CLASS_IDS, 0));
     std::vector<int64_t> ch_nc(TT + 1, 0);
@@ -1369,7 +1375,7 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
                 last = q;
             }
             const int id = pod_class_id(f, p->cpu0[i], p->mem0[i], p->pair0[i], p->xc_cpu ? p->xc_cpu + rc : nullptr,
-                                        p->xc_mem ? p->xc_mem + rc : nullptr, c->gi.n_gp);
+                                        p->xc_mem ? p->xc_mem + rc : nullptr, nx ? p->xp_pair + sp : nullptr, c->gi.n_gp);
             pid[i] = (int16_t)id;
             if (id >= 0) {
                 ++cn[id];
@@ -1397,29 +1403,21 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     std::vector<int> cls_of(POD_CLASS_IDS, -1);
     int64_t kt = 0, kbw = 0, kw = 0;
     for (int ord = 0; ord < POD_CLASS_IDS; ++ord) {
-        const int id = POD_CLASS_IDS - POD_SIG_IDS * (ord / POD_SIG_IDS + 1) + ord % POD_SIG_IDS;   // small, packed, plain
-        const int sig = id % POD_SIG_IDS;
+        const int id = pod_class_order(ord);               // small, packed, plain, inert
         // with spare slots requested every signature the K layout can hold gets a class, so
         // that inserts of shapes absent at load still land in place (plain: every signature of
-        // at most 3 records; packed: the 4 without records)
-        const bool holdable = id < POD_SIG_IDS ? (sig / 32) + ((sig / 8) % 4) + ((sig / 4) % 2) <= 3 : sig < 4;
-        if (!cnt[id] && !(c->spare_frac > 0 && holdable)) continue;
-        PodClass k;
-        std::memset(&k, 0, sizeof k);
-        k.nxp = (uint32_t)(sig % 4);
-        k.ovh = (uint32_t)((sig / 4) % 2);
-        k.xinit = (uint32_t)((sig / 8) % 4);
-        k.xreg = (uint32_t)(sig / 32);
-        k.packed = (uint32_t)(id / POD_SIG_IDS);
+        // at most 3 records; packed: the 4 without records).  An inert class is made for the
+        // pods it has, and has their spare room; one without pods waits for esc_pods_grow (until
+        // then a pod that turns inert takes a spare C slot, as a pod of a full class does)
+        if (!cnt[id] && !(c->spare_frac > 0 && id < POD_INERT_ID0 && pod_class_holdable(id))) continue;
+        PodClass k = pod_class_of_id(id);
         const int64_t want = cnt[id] + (c->spare_frac > 0 ? std::max<int64_t>(1, (int64_t)(cnt[id] * c->spare_frac)) : 0);
-        const int64_t R = k.xreg + k.xinit + k.ovh, tiles = (want + TILE - 1) / TILE;
+        const int64_t tiles = (want + TILE - 1) / TILE;
         k.t0 = kt;
         k.t1 = kt + tiles;
-        k.kind = k_kind((uint32_t)R, k.nxp, k.packed);
-        k.wt = k_tile_weight((uint32_t)R, k.nxp, k.packed);
         k.kb0 = kbw;
         k.w0 = kw;
-        kw += tiles * k.wt;
+        kw += tiles * kb_k1_wt(k);                         // (an inert class: none, K1 never reaches it)
         kt += tiles;
         kbw += tiles * (int64_t)k.wt * KB_UNIT;
         cls_of[id] = (int)cls.size();
@@ -1605,12 +1603,13 @@ int32_t esc_load_pods(esc_ctx* c, const esc_pod_soa* p, int64_t global_offset) {
     c->live_c_pods = n_c;
     c->live_xc = (int64_t)sc_c;                       // records K1 streams: the C pods' and the plain K pods'
     c->live_xp = p->n_xp;
-    c->live_pk_pods = c->live_p8_pods = c->live_p8_xp = 0;
+    c->live_pk_pods = c->live_p8_pods = c->live_p8_xp = c->live_inert_pods = c->live_inert_xp = 0;
     for (int id = 0; id < POD_CLASS_IDS; ++id) {
         if (cls_of[id] < 0) continue;
         if (id < POD_SIG_IDS) { c->live_xc += cnt[id] * (int64_t)kb_nrec(cls[cls_of[id]]); continue; }
         c->live_pk_pods += cnt[id];
         if (id >= 2 * POD_SIG_IDS) { c->live_p8_pods += cnt[id]; c->live_p8_xp += cnt[id] * (int64_t)cls[cls_of[id]].nxp; }
+        if (id >= POD_INERT_ID0) { c->live_inert_pods += cnt[id]; c->live_inert_xp += cnt[id] * (int64_t)cls[cls_of[id]].nxp; }
     }
     c->n_pods = n;
     c->k_tiles = k_tiles;
@@ -1859,10 +1858,12 @@ int32_t esc_stream_bytes(const esc_ctx* c, int64_t* pod_bytes, int64_t* node_byt
     // K1: flags 4 + cpu0 4 + mem0 8 + pair0 4 per pod, 16 per extra container record,
     // 4 per extra pair, 8 per C tile (record offsets); a pod of a packed class 12 B, of a
     // packed small class 8 B + 2 per extra pair, neither with records (live_xc counts the
-    // records stored: the folded ones are gone; esc_kernels.h, kp_*, kp8_*, kp_fold);
+    // records stored: the folded ones are gone; esc_kernels.h, kp_*, kp8_*, kp_fold); a pod
+    // of an inert class nothing: K1 never streams its tile (the inert pods are counted among
+    // the packed small ones, so their 8 B + 2 per extra pair come off again);
     // K2: see plan_node_layout (esc_node_layout.h)
     *pod_bytes = c->live_pods * 20 + c->live_xc * 16 + c->live_xp * 4 + c->c_tiles_loaded * 8 - c->live_pk_pods * 8 -
-                 c->live_p8_pods * 4 - c->live_p8_xp * 2;
+                 c->live_p8_pods * 4 - c->live_p8_xp * 2 - c->live_inert_pods * 8 - c->live_inert_xp * 2;
     *node_bytes = c->node_bytes;
     return ESC_OK;
 }
@@ -2645,6 +2646,7 @@ void remove_pod(esc_ctx* c, int64_t id, Patches& P) {
         c->live_xp -= k.nxp;
         if (k.packed) --c->live_pk_pods;
         if (k.packed == 2) { --c->live_p8_pods; c->live_p8_xp -= k.nxp; }
+        if (kb_inert(k)) { --c->live_inert_pods; c->live_inert_xp -= k.nxp; }
     }
     c->pod_cls[id] = -2;
     --c->live_pods;
@@ -3184,6 +3186,7 @@ int32_t upsert_apply(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, const
             c->live_xp -= k.nxp;
             if (k.packed) --c->live_pk_pods;
             if (k.packed == 2) { --c->live_p8_pods; c->live_p8_xp -= k.nxp; }
+            if (kb_inert(k)) { --c->live_inert_pods; c->live_inert_xp -= k.nxp; }
         }
         const PodClass& k = c->h_cls[ci];
         const int64_t q = c->pod_pos[id], sl = q % TILE;
@@ -3199,6 +3202,7 @@ int32_t upsert_apply(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, const
         c->live_xp += k.nxp;
         if (k.packed) ++c->live_pk_pods;
         if (k.packed == 2) { ++c->live_p8_pods; c->live_p8_xp += k.nxp; }
+        if (kb_inert(k)) { ++c->live_inert_pods; c->live_inert_xp += k.nxp; }
     }
     int32_t rc = apply_patches(c, P, pod_targets(c));
     if (!rc && touch_grew) rc = touch_upload(c);
@@ -3261,7 +3265,7 @@ int32_t batch_shape(const esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, 
         b.rof[i] = (int64_t)sc;
         b.pof[i] = (int64_t)sp;
         b.sid[i] = (int16_t)pod_class_id(f, p->cpu0[i], p->mem0[i], p->pair0[i], nc ? p->xc_cpu + sc : nullptr,
-                                         nc ? p->xc_mem + sc : nullptr, c->gi.n_gp);
+                                         nc ? p->xc_mem + sc : nullptr, nx ? p->xp_pair + sp : nullptr, c->gi.n_gp);
         sc += nc;
         sp += nx;
     }

@@ -10,7 +10,10 @@ into one effective request at load (``folded_request``); when that request fits 
 block too (``packed_mask``) the pod takes 12 B (pair0 | flags 4, cpu | mem 8) and no record
 bytes, and when it also fits the packed small block (``small_mask``) 8 B (cpu | mem | pair0 |
 flags in one u64) and 2 B per extra pair.  A K pod whose fold leaves the packed ranges keeps
-its records in the plain layout.
+its records in the plain layout.  A pod of the packed small block that no group can ever
+count (``inert_mask``: a daemonset pod, or one that blocks the default filter and has no group
+pair) sits in an inert class, which K1 never streams: 0 B.  An inert pod outside the packed
+small block is priced as any other pod of its layout.
 K2 reads the node index once per decision: per (label pair, node) entry of a pair some group
 selects 16 B when every node's allocatable cpu is in [0, 2^32) (one packed record: flags 4 +
 cpu 4 + mem 8), else 20 B (flags 4 + cpu 8 + mem 8), and 8 B per piece (offset + pair).
@@ -128,6 +131,25 @@ def small_mask(pods: dict, n_gp: int, _fold=None) -> np.ndarray:
     return packed_mask(pods, fold) & (cpu >= 0) & (cpu <= KP8_CPU_MAX) & (mem >= 0) & (mem <= KP8_MEM_MAX)
 
 
+def inert_mask(pods: dict, n_gp: int) -> np.ndarray:
+    """Pods no group can count, whatever the groups' state: daemonset pods (node_group.go:221,
+    :259), and pods that block the default filter (static, a selector, a blocking affinity)
+    none of whose pairs, pair0 and the extra ones, is a group pair (< n_gp).  A pod that does
+    not block the default filter joins the default slot: not inert."""
+    f = np.asarray(pods["flags"], np.uint64)
+    pair0 = np.asarray(pods["pair0"], np.uint32).astype(np.int64)
+    nxp = ((f >> 24) & 0x3F).astype(np.int64)
+    has_gp = pair0 < n_gp                                  # (NONE is 2^32 - 1: no group pair)
+    n_xp = int(nxp.sum())
+    if n_xp:
+        xp = np.asarray(pods["xp_pair"], np.uint32)[:n_xp].astype(np.int64)
+        owner = np.repeat(np.arange(len(f), dtype=np.int64), nxp)
+        has_gp |= np.bincount(owner[xp < n_gp], minlength=len(f)) > 0
+    daemonset = (f & 1) != 0
+    blocks = (f & 0b1110) != 0                             # static | has-selector | affinity-blocks-default
+    return daemonset | (blocks & ~has_gp)
+
+
 def pod_bytes(pods: dict, n_gp: int, lo: int = 0, hi: int | None = None) -> int:
     """K1's algorithmic bytes for pods [lo, hi) of a snapshot (one shard) in a context with
     n_gp group pairs."""
@@ -138,10 +160,11 @@ def pod_bytes(pods: dict, n_gp: int, lo: int = 0, hi: int | None = None) -> int:
     fold = folded_request(pods)
     pk = packed_mask(pods, fold)[lo:hi]
     sm = small_mask(pods, n_gp, fold)[lo:hi]
+    live = ~inert_mask(pods, n_gp)[lo:hi]                 # an inert small pod is never streamed
     c_tiles = (complex_pods(f[lo:hi]) + 63) // 64
     plain = (20 + 16 * nrec + 4 * nxp)[~pk].sum()
     packed = (12 + 4 * nxp)[pk & ~sm].sum()           # a packed pod's records are folded away
-    small = (8 + 2 * nxp)[sm].sum()
+    small = (8 + 2 * nxp)[sm & live].sum()
     return int(plain + packed + small + c_tiles * 8)
 
 

@@ -715,7 +715,7 @@ func (x *Context) PodsGrow(ids []int64, pods []*v1.Pod) error {
 // the free positions (-1: the id has no class) (esc_pods_room).
 func (x *Context) PodsRoom() (kCapacity, kFree, cFree int64, perClass []int64, err error) {
 	var a, b, d C.int64_t
-	perClass = make([]int64, 384)
+	perClass = make([]int64, 512)
 	err = rcErr("esc_pods_room", C.esc_pods_room(x.c, &a, &b, &d, (*C.int64_t)(unsafe.Pointer(ptr(perClass)))))
 	return int64(a), int64(b), int64(d), perClass, err
 }

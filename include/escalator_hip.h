@@ -367,7 +367,9 @@ int32_t esc_load_nodes(esc_ctx* ctx, const esc_node_soa* nodes, int64_t lo, int6
  * decisions (benchmarks use >1 so that timings are HBM-, not Infinity-Cache-, served). */
 int32_t esc_set_replicas(esc_ctx* ctx, int32_t n_replicas);
 /* Algorithmic HBM bytes one decision streams on this rank: K1 (pod shard) and K2
- * (this rank's node index share).  DESIGN.md §6; cross-checked by escalator_amd/layout.py. */
+ * (this rank's node index share).  DESIGN.md §6; cross-checked by escalator_amd/layout.py.
+ * The pods of the inert classes (below, the incremental snapshot) are not streamed and count
+ * no bytes. */
 int32_t esc_stream_bytes(const esc_ctx* ctx, int64_t* pod_bytes, int64_t* node_bytes);
 /* Sizes a host's per-pod and per-node arrays must match (esc_load_placement): pod ids
  * (esc_load_pods' count plus inserted ids) and node snapshot slots (loaded + added). */
@@ -492,7 +494,15 @@ int32_t esc_hbm_probe(esc_ctx* ctx, int64_t bytes, int32_t reps, double* read_gb
  * a pod whose values and whose effective request (ComputePodResourceRequest, evaluated
  * once, at the load or the upsert: a pod's container requests do not change without an
  * event) fit the packed ranges is stored as that one request in the packed class of its
- * pair count, every other pod with its records in the class of its record signature; a
+ * pair count, every other pod with its records in the class of its record signature.  A
+ * pod of the packed small class (request below 2^14 m and 2^34 B) that no group can ever
+ * count — a daemonset pod, or one that blocks the default filter (static, a selector, a
+ * blocking affinity) and none of whose pairs is a group's — is stored in the inert class of
+ * its pair count (class id pairs | 3 << 7): the same tile, which the per-decision pod pass
+ * never streams.  The mask depends on the pod and the context's group pairs alone; an upsert
+ * that changes it moves the pod between classes like any other change of class.  An inert
+ * class exists from the load when the snapshot has such pods (with their spare room) and is
+ * otherwise made by esc_pods_grow.  A
  * pod with > 3 container records or > 3 extra pairs (or whose
  * class is full) stays in its own C-section slot when that has room, else takes a spare
  * C slot (room for 4 extra regular and 2 init containers, an overhead and 6 extra pairs;
@@ -516,8 +526,8 @@ int32_t esc_pods_delete(esc_ctx* ctx, const int64_t* ids, int64_t n);
  *   free positions and arr_i arrivals that need a new position,
  *     want_i = live_i + arr_i + s(live_i + arr_i),  s(x) = f > 0 ? max(1, floor(x * f)) : 0,
  *     tiles_i = max(old tiles_i, ceil(want_i / 256))       (f: esc_set_spare's fraction).
- *   A class the batch needs and the context lacks (possible only when it was loaded with f = 0)
- *   is appended behind the existing ones, in ascending class id.  Tile ranges are re-cut in
+ *   A class the batch needs and the context lacks (it was loaded with f = 0, or the class is an
+ *   inert one the load had no pods for) is appended behind the existing ones, in ascending class id.  Tile ranges are re-cut in
  *   class-index order.
  *   C section.  arr_c = batch pods with > 3 records or > 3 extra pairs that cannot stay in
  *   their own slot; one that a spare slot cannot hold makes the call ESC_E_LIMIT (that pod
@@ -536,11 +546,11 @@ int32_t esc_pods_delete(esc_ctx* ctx, const int64_t* ids, int64_t n);
  * esc_load_pods or on a stale context.  Multi-device: every device's share of the batch is
  * checked before any device grows; the ranks of a sharded job each grow their own shard.
  * esc_pods_room reports (any pointer may be NULL) the K positions in all, the free ones, the
- * free C slots and, per class id (384 of them), the free positions, -1 where the id has no
+ * free C slots and, per class id (512 of them), the free positions, -1 where the id has no
  * class; multi-device: summed over the devices.                                        */
 int32_t esc_pods_grow(esc_ctx* ctx, const int64_t* ids, const esc_pod_soa* pods);
 int32_t esc_pods_room(const esc_ctx* ctx, int64_t* k_capacity, int64_t* k_free, int64_t* c_free,
-                      int64_t* per_class /* [384] or NULL */);
+                      int64_t* per_class /* [512] or NULL */);
 int32_t esc_nodes_update(esc_ctx* ctx, const int64_t* ids, int64_t n, const uint32_t* flags,
                          const int64_t* cpu_m, const int64_t* mem_b);
 /* Node additions and deletions (the node informer's Add / Delete, pkg/k8s/cache.go:37-56)
