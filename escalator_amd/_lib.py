@@ -93,6 +93,14 @@ class AuditReport(C.Structure):
     _fields_ = [("ran", u32), ("skipped", u32), ("check", AuditCheck * len(AUDIT_CHECKS))]
 
 
+PODS_COMPACT_FIELDS = ["rehomed", "classes_created", "k_tiles_before", "k_tiles_after", "k1_bytes_before",
+                       "k1_bytes_after", "moved", "c_free_before", "c_free_after"]
+
+
+class PodsCompactReport(C.Structure):
+    _fields_ = [(n, i64) for n in PODS_COMPACT_FIELDS]
+
+
 class KV(C.Structure):
     _fields_ = [("key", cstr), ("value", cstr)]
 
@@ -187,6 +195,9 @@ _SIGS = {
     "esc_pods_delete": (i32, [VP, P(i64), i64]),
     "esc_pods_grow": (i32, [VP, P(i64), P(PodSoA)]),
     "esc_pods_room": (i32, [VP, P(i64), P(i64), P(i64), P(i64)]),
+    "esc_pods_compact": (i32, [VP, P(PodsCompactReport)]),
+    "esc_pods_slack": (i32, [VP, P(i64), P(i64), P(i64)]),
+    "esc_pod_where": (i32, [VP, i64, P(i32), P(i64)]),
     "esc_nodes_update": (i32, [VP, P(i64), i64, P(u32), P(i64), P(i64)]),
     "esc_nodes_add": (i32, [VP, P(NodeSoA), P(i64)]),
     "esc_nodes_delete": (i32, [VP, P(i64), i64]),

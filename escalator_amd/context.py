@@ -299,6 +299,31 @@ class Context:
                                        per.ctypes.data_as(C.POINTER(C.c_int64))), "esc_pods_room")
         return {"k_capacity": a.value, "k_free": b.value, "c_free": d.value, "per_class": per}
 
+    def pods_compact(self) -> dict:
+        """The pod side re-laid on the device (esc_pods_compact): K-holdable pods parked in C
+        slots go back to their classes, every class is re-cut to the load's rule over its live
+        pods and its pods re-sorted by column bucket.  Pod ids and the placement stay.  Returns
+        the report: ``rehomed``, ``classes_created``, ``k_tiles_before`` / ``_after``,
+        ``k1_bytes_before`` / ``_after``, ``moved``, ``c_free_before`` / ``_after``."""
+        rep = L.PodsCompactReport()
+        L.check(self.lib.esc_pods_compact(self.handle, C.byref(rep)), "esc_pods_compact")
+        return {n: int(getattr(rep, n)) for n in L.PODS_COMPACT_FIELDS}
+
+    def pods_slack(self) -> dict:
+        """esc_pods_slack (host only): ``k_tiles`` resident, ``k_tiles_rule`` the tiles the
+        load's rule cuts for the present live counts, ``parked`` the live pods in C slots with
+        at most 3 records and 3 pairs."""
+        a, b, d = C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self.lib.esc_pods_slack(self.handle, C.byref(a), C.byref(b), C.byref(d)), "esc_pods_slack")
+        return {"k_tiles": a.value, "k_tiles_rule": b.value, "parked": d.value}
+
+    def pod_where(self, pod_id: int) -> tuple[int, int]:
+        """esc_pod_where (host only): the pod's class id (-1: the C section, -2: absent) and its
+        position inside the class, or its C-array index."""
+        cid, pos = C.c_int32(), C.c_int64()
+        L.check(self.lib.esc_pod_where(self.handle, int(pod_id), C.byref(cid), C.byref(pos)), "esc_pod_where")
+        return cid.value, pos.value
+
     def pods_delete(self, ids):
         ids = np.ascontiguousarray(ids, np.int64)
         L.check(self.lib.esc_pods_delete(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids)),

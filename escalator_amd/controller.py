@@ -476,13 +476,18 @@ class ResidentController(Controller):
     ``pod_grow=True``: a ``pods_upsert`` of more pods than the load left room for is answered by
     ``ctx.pods_grow()`` with the same batch and one retry before any reload
     (``events.pod_grows`` / ``events.pod_grow_causes``).  Pod ids, the placement, the trackers
-    and the instantiation times stay; the next decision runs on a re-planned K1 grid."""
+    and the instantiation times stay; the next decision runs on a re-planned K1 grid.
+
+    ``pod_compact=frac`` (off by default, ``None``): after a flush that applied cleanly the pod
+    side is re-laid by ``ctx.pods_compact()`` when ``ctx.pods_slack()`` reports free tiles beyond
+    the load's rule plus parked pods of at least ``frac`` of the live pods
+    (``events.pod_compacts`` / ``events.pod_compact_causes``).  Pod ids and the placement stay."""
 
     REBUILT_CHECKS = ("ENTRY", "FIRST", "REGION", "OCC", "TRACKER")
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
                  selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0, node_rebuild: bool = False,
-                 node_compact: bool = False, pod_grow: bool = False):
+                 node_compact: bool = False, pod_grow: bool = False, *, pod_compact: float | None = None):
         super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
                          selection_slack=selection_slack)
         from .events import EventQueue
@@ -491,7 +496,7 @@ class ResidentController(Controller):
         self.node_rebuild = bool(node_rebuild) or self.node_compact
         self.pod_grow = bool(pod_grow)
         self.events = EventQueue(spare=self.spare, rebuild=self.node_rebuild, compact=self.node_compact,
-                                 pod_grow=self.pod_grow)
+                                 pod_grow=self.pod_grow, pod_compact=pod_compact)
         # the resync of the derived state (the reference's informers resync hourly,
         # pkg/k8s/cache.go:27,48): every audit_every-th scan audits the snapshot after the flush
         # and reloads it once when a check finds a mismatch; 0 = never

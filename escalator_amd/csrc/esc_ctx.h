@@ -3,6 +3,8 @@
 //                     reaping
 //   esc_rebuild.hip   the device rebuild of the node side, the node table's compaction, the audit
 //   esc_pod_grow.hip  the pod classes grown on the device (esc_pods_grow, esc_pods_room)
+//   esc_pod_compact.hip  the pod side re-laid on the device (esc_pods_compact, esc_pods_slack,
+//                     esc_pod_where)
 // Everything else (esc_multi.hip, esc_list.hip, the packer, the generator) sees esc_ctx as
 // opaque.  Helpers that cross a file are declared at the end, each defined in the file of its
 // subsystem; the small ones are inline here.
@@ -260,6 +262,7 @@ struct esc_ctx {
     // patch applications fail after their host-side writes
     int lb_fail_order = 0, lb_fail_list = 0, fail_patches = 0;
     int fail_grow = 0;                                        // the next n esc_pods_grow fail before their swap
+    int fail_compact = 0;                                     // the next n esc_pods_compact fail before their swap
     uint32_t *d_pstart = nullptr, *d_plen = nullptr;
     uint32_t* d_ord = nullptr;                                // K5 output, in the group regions
     esc::OrdChunk* d_pchunks = nullptr;                       // packed chunks of small groups
@@ -429,6 +432,9 @@ int32_t ensure_ne_dev(esc_ctx* c);
 int32_t occ_recount(esc_ctx* c);
 void release_work(esc_ctx* c);
 int32_t ensure_work(esc_ctx* c);
+// Rewrites the PodRefs of the bound pods among ids from their present slots (esc_pods_compact:
+// the pods that left the C section).
+int32_t refresh_podrefs(esc_ctx* c, std::vector<int64_t>& ids);
 // A pod event batch as esc_pods_upsert and esc_pods_grow both read it: validated, each pod's
 // first record / extra pair in the batch and its class id (pod_class_id).
 struct BatchShape {

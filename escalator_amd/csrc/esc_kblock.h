@@ -207,6 +207,40 @@ ESC_KB_HD uint32_t kp_fold(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pai
     if (n_gp < KP8_PAIR_NONE && kp8_fits(cpu, mem)) return 2;
     return kp_val_fits(cpu, mem, false) ? 1 : 0;
 }
+// Can no group ever count the pod, whatever the groups' state?  A daemonset pod is excluded
+// by both filters (node_group.go:221, :259); a pod that blocks the default filter (static, a
+// selector, a blocking affinity) joins only the slots of its pairs, so it is inert when none
+// of them is a group pair (< n_gp).  A pod that does not block the default filter joins the
+// default slot and is never inert.  (escalator_amd/layout.py inert_mask restates it.)  Host and
+// device: esc_pods_compact classifies the pods it re-homes on the device.
+ESC_KB_HD bool pod_inert(uint32_t f, uint32_t pair0, const uint32_t* xp, uint32_t n_gp) {
+    if (f & ESC_PF_DAEMONSET) return true;
+    if (!(f & (ESC_PF_STATIC | ESC_PF_HAS_SEL | ESC_PF_AFF_BLOCK))) return false;
+    if (pair0 < n_gp) return false;
+    for (uint32_t k = 0, np = pf_xpair(f); k < np; ++k)
+        if (xp[k] < n_gp) return false;
+    return true;
+}
+
+// K class of a pod, the one place that decides it: -1 for the C section (more
+// than 3 extra container records or more than 3 extra pairs); else the fold (kp_fold) either
+// packs the pod's effective request — class id = its pair count np | packed << 7, packed 2
+// for the packed small block and 1 for the packed block, a signature without records — or
+// leaves the pod its records in the plain class of its own signature.  xc_cpu / xc_mem: the
+// pod's own records (null when it has none).  xp: its extra pairs (null when it has none).  A
+// pod of the packed small block that is inert (pod_inert) takes the inert class of its pair
+// count instead, id np | 3 << 7: the same tile, kept out of K1's stream.
+ESC_KB_HD int pod_class_id(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
+                        const int64_t* xc_mem, const uint32_t* xp, uint32_t n_gp) {
+    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, np = pf_xpair(f);
+    if (xr + xi + ov > 3 || np > 3) return -1;
+    int64_t cpu, mem;
+    const uint32_t packed = kp_fold(f, cpu0, mem0, pair0, xc_cpu, xc_mem, n_gp, cpu, mem);
+    if (packed == 2 && pod_inert(f, pair0, xp, n_gp)) return (int)(np | POD_INERT_ID0);
+    if (packed) return (int)(np | packed * POD_SIG_IDS);
+    return (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
+}
+
 // The head of K pod s of the block at word blk, any layout: ESC_PF_* flags (the class
 // signature's counts included; a packed small pod's static / has-selector / affinity bits
 // read back as ESC_PF_HAS_SEL), pair0 (NONE: none, or no group's in a small block) and the
@@ -297,5 +331,26 @@ struct KbRegrowCls {
     uint32_t wt, pad;
 };
 static_assert(sizeof(KbRegrowCls) == 56, "k_kb_regrow reads the staged table as 8-B words");
+
+// esc_pods_compact: one class of the re-cut K section as k_pc_move reads it.  The
+// class's live pods are elements [start, start + live) of the sorted (class, bucket, source)
+// elements and take positions [0, live) of its tiles; a position past them copies the same slot
+// of the class's free tile at word tmpl of the staged templates (-1: the class has no tile).
+struct PcCls {
+    int64_t start, live;
+    int64_t tmpl, pad;
+};
+// The pod of a K-holdable C slot as its own shape (its records and pairs first of each kind in
+// the slot's room, the rest neutral): what pod_class_id and kb_write_pod take.
+struct CPod {
+    uint32_t f, cpu0, pair0, ok;       // ok: at most 3 own records and 3 own pairs
+    int64_t mem0;
+};
+struct CPodRec {                       // its records (regular, init, overhead side by side) and pairs; one per
+    int64_t xc[3], xm[3];              // lane in LDS, so that the shared rule's loops index memory, not registers
+    uint32_t xp[3], pad;
+};
+static_assert(sizeof(CPodRec) == 64, "one LDS row per lane");
+constexpr uint32_t K_TILE_WEIGHT_MAX = k_tile_weight(3, 3);   // the heaviest tile (plain, 3 records, 3 pairs)
 
 }  // namespace esc

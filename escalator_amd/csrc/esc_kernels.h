@@ -485,6 +485,46 @@ struct KbRegrow {
     uint32_t* err;
 };
 hipError_t launch_kb_regrow(const KbRegrow& r, int64_t n_tiles, hipStream_t st);
+// esc_pods_compact: the K-holdable C slots classified (k_pc_classify), every
+// old K position and re-homed slot keyed (class, bucket) with its source as the element's low
+// word (k_pc_keys) and stable-sorted by the key (the age index's LSD passes), the new tiles
+// gathered in that order (k_pc_move, one workgroup per new tile), the vacated C slots freed in
+// place after the swap (k_pc_cfree).  `old` is the resident replica; sizes in elements.  A
+// source, a class or a block that does not fit its buffer sets bits of *err and is not indexed.
+struct PodCompactDev {
+    PodDev old;
+    int64_t n_xc, n_xp;                // sizes of old.xc_cpu / xc_mem and old.xp
+    int64_t old_words;                 // old.kb, in u32 words
+    const uint32_t* free_bits;         // [ceil(old.k_tiles * 256 / 32)] bit set: the old K slot is free
+    const uint32_t* cand;              // [n_cand] the K-holdable C slots (C-array index), ascending
+    const uint32_t* cand_used;         // [n_cand] the host's count of the pod's own records | pairs << 16 (h_cused)
+    int32_t* cand_id;                  // [n_cand] k_pc_classify: class id (pod_class_id), -1: stays
+    const int32_t* cand_cls;           // [n_cand] the host's: new class index, -1: stays
+    int64_t n_cand;
+    uint32_t n_gp, pod_sort;
+    int64_t nbk;                       // buckets per class (pod_buckets)
+    // the re-cut K section
+    const PodClass* cls;               // [n_cls] the new class table
+    const PcCls* tab;                  // [n_cls]
+    const uint32_t* tmpl;              // the classes' free tiles
+    int64_t tmpl_words;
+    int32_t n_cls;
+    int64_t k_tiles;                   // new K tiles
+    uint32_t* kb;                      // the new K blocks
+    int64_t kb_words;
+    uint32_t* map_k;                   // [old.k_tiles * 256] old slot -> new position in its class (NONE: free)
+    uint32_t* map_c;                   // [n_cand] re-homed slot -> its position (NONE: stays)
+    uint32_t* err;
+};
+hipError_t launch_pc_classify(const PodCompactDev& d, hipStream_t st);
+// elems[2]: old.k_tiles * 256 + n_cand 8-B elements each; hist: sort_hist_words of that count;
+// tot: 256 words; key_bits: bits of n_cls * nbk.  *sorted: the buffer that holds the order.
+hipError_t launch_pc_order(const PodCompactDev& d, uint64_t* elems[2], uint32_t* hist, uint32_t* tot, int key_bits,
+                           int* sorted, hipStream_t st);
+hipError_t launch_pc_move(const PodCompactDev& d, const uint64_t* sorted, hipStream_t st);
+// The C arrays of one replica (written in place): the re-homed slots become free ones.
+hipError_t launch_pc_cfree(const PodCompactDev& d, uint32_t* flags, int64_t* xc_cpu, int64_t* xc_mem, uint32_t* xp,
+                           hipStream_t st);
 // The bounded waits of the decoupled look-backs (k_ord_split, k_memb_keys): HIP does not
 // promise dispatch order, so a chunk never waits unboundedly on one that was not dispatched.
 // A chunk that waited `spins` probes gives up: it publishes a FAILED status word (never an

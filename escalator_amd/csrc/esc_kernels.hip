@@ -3619,7 +3619,270 @@ __global__ __launch_bounds__(256) void k_kb_regrow(KbRegrow R) {
     }
 }
 
+// ===================================================================== pod classes compacted
+// esc_pods_compact (PodCompactDev, esc_kernels.h).  Every offset a kernel derives
+// from device words is checked against its buffer's size before it indexes; a violation sets a
+// bit of *err, read at the call's one wait, and nothing is swapped.
+namespace {
+constexpr uint32_t PC_ERR_SLOT = 1u, PC_ERR_CLASS = 2u, PC_ERR_SRC = 4u, PC_ERR_DST = 8u, PC_ERR_ORDER = 16u;
+
+// The pod in C slot d in its own shape (CPod).  The slot's flags carry the slot's room; the
+// pod's records are the first of each kind, the rest neutral (0 for regular containers and the
+// overhead, both keys absent for init containers), its pairs the first `used >> 16` (the host's
+// count).  The host knows how many records the pod has (`used & 0xFFFF`) but not their kinds, so
+// the kinds are read from the values: a kind's records reach to its last one that is not neutral.
+// A real record that equals the neutral one is read as absent (it adds nothing to any sum; in a
+// plain class the pod then takes the signature without it).  More records than the host counted
+// means the mirrors and the device disagree: false, as for a slot or records outside the arrays
+// (nothing is read there).
+__device__ bool c_slot_pod(const PodCompactDev& D, uint32_t d, uint32_t used, CPod& p, CPodRec& r) {
+    const PodDev& P = D.old;
+    p.ok = 0;
+    if ((int64_t)d >= P.c_tiles * CTILE) return false;
+    const int64_t t = d / CTILE, l = d % CTILE;
+    int64_t ro = P.xc_base[t], po = P.xp_base[t];
+    for (int64_t k = 0; k < l; ++k) {
+        const uint32_t g = P.flags[t * CTILE + k];
+        ro += pf_xctr(g);
+        po += pf_xpair(g);
+    }
+    const uint32_t cf = P.flags[d];
+    const uint32_t cr = pf_xreg(cf), ci = pf_xinit(cf), cv = (cf & ESC_PF_HAS_OVH) ? 1u : 0u, cp = pf_xpair(cf);
+    if (ro + cr + ci + cv > D.n_xc || po + cp > D.n_xp) return false;
+    uint32_t xr = 0, xi = 0, ov = 0, np = 0;
+    for (uint32_t k = 0; k < cr; ++k)
+        if (P.xc_cpu[ro + k] != 0 || P.xc_mem[ro + k] != 0) xr = k + 1;
+    for (uint32_t k = 0; k < ci; ++k)
+        if (P.xc_cpu[ro + cr + k] != INT64_MIN || P.xc_mem[ro + cr + k] != INT64_MIN) xi = k + 1;
+    if (cv && (P.xc_cpu[ro + cr + ci] != 0 || P.xc_mem[ro + cr + ci] != 0)) ov = 1;
+    np = used >> 16;
+    if (np > cp || xr + xi + ov > (used & 0xFFFFu)) return false;
+    p.f = (cf & KP_POD_FLAGS) | (ov ? ESC_PF_HAS_OVH : 0u) | xr << ESC_PF_XREG_SHIFT | xi << ESC_PF_XINIT_SHIFT |
+          np << ESC_PF_XPAIR_SHIFT;
+    p.cpu0 = P.cpu0[d];
+    p.mem0 = P.mem0[d];
+    p.pair0 = P.pair0[d];
+    const uint32_t n = xr + xi + ov;
+    p.ok = n <= 3 && np <= 3;
+#pragma unroll
+    for (uint32_t j = 0; j < 3; ++j) {                   // its own records side by side: regular, init, overhead
+        const int64_t at = j < xr ? ro + j : (j < xr + xi ? ro + cr + (j - xr) : ro + cr + ci);
+        const bool have = p.ok && j < n;
+        r.xc[j] = have ? P.xc_cpu[at] : 0;
+        r.xm[j] = have ? P.xc_mem[at] : 0;
+        r.xp[j] = p.ok && j < np ? P.xp[po + j] : NONE;
+    }
+    return true;
+}
+
+// class of old K tile t (the last class that starts at or before it; checked by the caller)
+__device__ __forceinline__ int pc_tile_class(const PodClass* cls, int n_cls, int64_t t) {
+    int ci = 0;
+    for (int hi = n_cls; hi - ci > 1;) {
+        const int mid = (ci + hi) >> 1;
+        if (cls[mid].t0 <= t) ci = mid;
+        else hi = mid;
+    }
+    return ci;
+}
+
+// Every word of slot ss of the block at word sblk of src, copied to slot ds of the tile staged
+// at dst (block-relative, the same class): the rows of the class's format, element by element.
+__device__ __forceinline__ void pc_copy_slot(const PodClass& C, const uint32_t* __restrict__ src, int64_t sblk,
+                                             int64_t ss, uint32_t* dst, int64_t ds) {
+    const int64_t* s64 = reinterpret_cast<const int64_t*>(src);
+    const uint16_t* s16 = reinterpret_cast<const uint16_t*>(src);
+    int64_t* d64 = reinterpret_cast<int64_t*>(dst);
+    uint16_t* d16 = reinterpret_cast<uint16_t*>(dst);
+    const int64_t sp = kb_pos64(ss), dp = kb_pos64(ds);
+    if (C.packed == 2) {
+        d64[dp] = __builtin_nontemporal_load(s64 + sblk / 2 + sp);
+        for (uint32_t k = 0; k < C.nxp; ++k) d16[kb_xp(C, 0, k, ds)] = __builtin_nontemporal_load(s16 + kb_xp(C, sblk, k, ss));
+        return;
+    }
+    if (C.packed) {
+        dst[ds] = __builtin_nontemporal_load(src + sblk + ss);
+        d64[KP_CM0 / 2 + dp] = __builtin_nontemporal_load(s64 + (sblk + KP_CM0) / 2 + sp);
+    } else {
+        dst[ds] = __builtin_nontemporal_load(src + sblk + ss);
+        dst[KB_CPU0 + ds] = __builtin_nontemporal_load(src + sblk + KB_CPU0 + ss);
+        d64[KB_MEM0 / 2 + dp] = __builtin_nontemporal_load(s64 + (sblk + KB_MEM0) / 2 + sp);
+        dst[KB_PAIR0 + ds] = __builtin_nontemporal_load(src + sblk + KB_PAIR0 + ss);
+        const uint32_t R = kb_nrec(C);
+        for (uint32_t k = 0; k < R; ++k) {
+            const int64_t so = kb_rec64(sblk, k, ss), o = kb_rec64(0, k, ds);
+            d64[o] = __builtin_nontemporal_load(s64 + so);
+            d64[o + 256] = __builtin_nontemporal_load(s64 + so + 256);
+        }
+    }
+    for (uint32_t k = 0; k < C.nxp; ++k) dst[kb_xp(C, 0, k, ds)] = __builtin_nontemporal_load(src + kb_xp(C, sblk, k, ss));
+}
+}  // namespace
+
+// One lane per K-holdable C slot: its class id by the one definition (pod_class_id).
+__global__ __launch_bounds__(256) void k_pc_classify(PodCompactDev D) {
+    __shared__ CPodRec recs[256];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D.n_cand) return;
+    CPod p;
+    CPodRec& r = recs[threadIdx.x];
+    if (!c_slot_pod(D, D.cand[i], D.cand_used[i], p, r)) {
+        rb_fail(D.err, PC_ERR_SLOT);
+        D.cand_id[i] = -1;
+        return;
+    }
+    D.cand_id[i] = p.ok ? pod_class_id(p.f, p.cpu0, p.mem0, p.pair0, r.xc, r.xm, r.xp, D.n_gp) : -1;
+}
+
+// One lane per old K slot, then per candidate: the element (class * nbk + bucket) << 32 | source
+// (the old slot, or old K slots + the candidate's index).  A free slot and a candidate that
+// stays take the key past every class's (n_cls * nbk), so the sort leaves them last.
+__global__ __launch_bounds__(256) void k_pc_keys(PodCompactDev D, uint64_t* __restrict__ elems) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nk = D.old.k_tiles * TILE;
+    if (i >= nk + D.n_cand) return;
+    const uint64_t dead = (uint64_t)D.n_cls * (uint64_t)D.nbk;
+    uint64_t key = dead;
+    if (i < nk) {
+        if (!((D.free_bits[i >> 5] >> (i & 31)) & 1u)) {
+            const int64_t t = i / TILE;
+            const int ci = pc_tile_class(D.old.cls, D.old.n_cls, t);
+            const PodClass C = D.old.cls[ci];
+            const int64_t blk = kb_block(C, t);
+            if (D.old.n_cls <= 0 || t < C.t0 || t >= C.t1 || blk < 0 || blk + (int64_t)C.wt * KB_UNIT > D.old_words) {
+                rb_fail(D.err, PC_ERR_CLASS);
+            } else {
+                const uint32_t q0 = kb_head(C, D.old.kb, blk, i % TILE).pair0;
+                const uint64_t b = D.pod_sort ? (q0 < D.n_gp ? (uint64_t)(q0 / D.pod_sort) : (uint64_t)D.nbk - 1) : 0;
+                key = (uint64_t)ci * (uint64_t)D.nbk + b;
+            }
+        }
+    } else {
+        const int64_t j = i - nk;
+        const int32_t ci = D.cand_cls[j];
+        const uint32_t d = D.cand[j];
+        if (ci >= 0 && ci < D.n_cls && (int64_t)d < D.old.c_tiles * CTILE) {
+            const uint32_t q0 = D.old.pair0[d];
+            const uint64_t b = D.pod_sort ? (q0 < D.n_gp ? (uint64_t)(q0 / D.pod_sort) : (uint64_t)D.nbk - 1) : 0;
+            key = (uint64_t)ci * (uint64_t)D.nbk + b;
+        } else if (ci >= 0) {
+            rb_fail(D.err, PC_ERR_SLOT);
+        }
+    }
+    elems[i] = key << 32 | (uint64_t)(uint32_t)i;
+}
+
+// One 256-thread workgroup per NEW K tile, one thread per slot.  The slot's pod is element
+// start + position of the sorted order: a resident pod's words are gathered row by row from its
+// old tile (nontemporal loads; positions ascend inside a bucket, so neighbouring lanes read
+// neighbouring elements), a re-homed pod is written from its C slot as kb_write_pod writes it,
+// and a position past the class's live pods copies the class's free tile.  The tile is staged in
+// LDS (at most 20 KB, beside 16 KB of re-homed pods' records) and stored whole, 16 B per lane and round.  The thread also writes its
+// pod's entry of the old -> new map.
+__global__ __launch_bounds__(256) void k_pc_move(PodCompactDev D, const uint64_t* __restrict__ sorted) {
+    __shared__ __attribute__((aligned(16))) uint32_t tile[K_TILE_WEIGHT_MAX * KB_UNIT];
+    __shared__ CPodRec recs[256];
+    const int64_t t = blockIdx.x;
+    const int ci = pc_tile_class(D.cls, D.n_cls, t);
+    if (D.n_cls <= 0 || t < D.cls[ci].t0 || t >= D.cls[ci].t1) {
+        if (threadIdx.x == 0) rb_fail(D.err, PC_ERR_CLASS);
+        return;
+    }
+    const PodClass C = D.cls[ci];
+    const PcCls T = D.tab[ci];
+    const int64_t words = (int64_t)C.wt * KB_UNIT, dst = kb_block(C, t);
+    if (C.wt > K_TILE_WEIGHT_MAX || dst < 0 || (dst & 3) || dst + words > D.kb_words || T.tmpl < 0 ||
+        T.tmpl + words > D.tmpl_words) {
+        if (threadIdx.x == 0) rb_fail(D.err, PC_ERR_DST);
+        return;
+    }
+    const int64_t s = threadIdx.x, q = (t - C.t0) * TILE + s, nk = D.old.k_tiles * TILE;
+    bool placed = false;
+    if (q < T.live) {
+        const uint64_t e = sorted[T.start + q];
+        const int64_t src = (int64_t)(uint32_t)e;
+        if ((e >> 32) / (uint64_t)D.nbk != (uint64_t)ci) {
+            rb_fail(D.err, PC_ERR_ORDER);                  // the device counted other live pods than the host
+        } else if (src < nk) {
+            const int64_t ts = src / TILE;
+            const PodClass O = ci < D.old.n_cls ? D.old.cls[ci] : C;
+            const int64_t sblk = kb_block(O, ts);
+            if (ci >= D.old.n_cls || ts < O.t0 || ts >= O.t1 || O.wt != C.wt || sblk < 0 || sblk + words > D.old_words) {
+                rb_fail(D.err, PC_ERR_SRC);
+            } else {
+                pc_copy_slot(C, D.old.kb, sblk, src % TILE, tile, s);
+                D.map_k[src] = (uint32_t)q;
+                placed = true;
+            }
+        } else {
+            const int64_t j = src - nk;
+            CPod p;
+            CPodRec& r = recs[threadIdx.x];
+            if (j >= D.n_cand || !c_slot_pod(D, D.cand[j], D.cand_used[j], p, r) || !p.ok) {
+                rb_fail(D.err, PC_ERR_SRC);
+            } else {
+                kb_write_pod(C, 0, s, p.f, p.cpu0, p.mem0, p.pair0, r.xc, r.xm, r.xp, [&](int width, int64_t at, uint64_t v) {
+                    if (width == 8) reinterpret_cast<int64_t*>(tile)[at] = (int64_t)v;
+                    else if (width == 4) tile[at] = (uint32_t)v;
+                    else reinterpret_cast<uint16_t*>(tile)[at] = (uint16_t)v;
+                });
+                D.map_c[j] = (uint32_t)q;
+                placed = true;
+            }
+        }
+    }
+    if (!placed) pc_copy_slot(C, D.tmpl, T.tmpl, s, tile, s);
+    __syncthreads();
+    const v4u32* __restrict__ l16 = reinterpret_cast<const v4u32*>(tile);
+    v4u32* __restrict__ d16 = reinterpret_cast<v4u32*>(D.kb + dst);
+    const int n16 = (int)(words / 4);
+    for (int k = (int)threadIdx.x; k < n16; k += 256) d16[k] = l16[k];
+}
+
+// One lane per re-homed C slot of one replica's C arrays: free as esc_pods_delete leaves a slot
+// (the daemonset flag, the counts kept as its room), its records neutral and its pairs NONE.
+__global__ __launch_bounds__(256) void k_pc_cfree(PodCompactDev D, uint32_t* __restrict__ flags, int64_t* __restrict__ xc_cpu,
+                                                  int64_t* __restrict__ xc_mem, uint32_t* __restrict__ xp) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D.n_cand || D.cand_cls[i] < 0) return;
+    const uint32_t d = D.cand[i];
+    if ((int64_t)d >= D.old.c_tiles * CTILE) return;
+    const int64_t t = d / CTILE, l = d % CTILE;
+    int64_t ro = D.old.xc_base[t], po = D.old.xp_base[t];
+    for (int64_t k = 0; k < l; ++k) {
+        const uint32_t g = flags[t * CTILE + k];
+        ro += pf_xctr(g);
+        po += pf_xpair(g);
+    }
+    const uint32_t cf = flags[d];
+    const uint32_t cr = pf_xreg(cf), ci = pf_xinit(cf), n = pf_xctr(cf), cp = pf_xpair(cf);
+    if (ro + n > D.n_xc || po + cp > D.n_xp) return;
+    for (uint32_t k = 0; k < n; ++k) xc_cpu[ro + k] = xc_mem[ro + k] = (k >= cr && k < cr + ci) ? INT64_MIN : 0;
+    for (uint32_t k = 0; k < cp; ++k) xp[po + k] = NONE;
+    flags[d] = cf | ESC_PF_DAEMONSET;
+}
+
 // ===================================================================== launchers
+hipError_t launch_pc_classify(const PodCompactDev& d, hipStream_t st) {
+    if (d.n_cand <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pc_classify, dim3((unsigned)((d.n_cand + 255) / 256)), dim3(256), 0, st, d);
+    return hipGetLastError();
+}
+
+hipError_t launch_pc_move(const PodCompactDev& d, const uint64_t* sorted, hipStream_t st) {
+    if (d.k_tiles <= 0) return hipSuccess;
+    if (d.k_tiles > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pc_move, dim3((unsigned)d.k_tiles), dim3(256), 0, st, d, sorted);
+    return hipGetLastError();
+}
+
+hipError_t launch_pc_cfree(const PodCompactDev& d, uint32_t* flags, int64_t* xc_cpu, int64_t* xc_mem, uint32_t* xp,
+                           hipStream_t st) {
+    if (d.n_cand <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pc_cfree, dim3((unsigned)((d.n_cand + 255) / 256)), dim3(256), 0, st, d, flags, xc_cpu, xc_mem, xp);
+    return hipGetLastError();
+}
+
 hipError_t launch_kb_regrow(const KbRegrow& r, int64_t n_tiles, hipStream_t st) {
     if (n_tiles <= 0) return hipSuccess;
     if (n_tiles > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
@@ -3918,6 +4181,26 @@ hipError_t launch_nodes_rebuild(const RebuildDev& r, uint64_t* elems[2], uint32_
         src ^= 1;
     }
     hipLaunchKernelGGL(k_entry_place, dim3((unsigned)((r.n_elems + 255) / 256)), dim3(256), 0, st, r, elems[src]);
+    return hipGetLastError();
+}
+
+hipError_t launch_pc_order(const PodCompactDev& d, uint64_t* elems[2], uint32_t* hist, uint32_t* tot, int key_bits,
+                           int* sorted, hipStream_t st) {
+    *sorted = 0;
+    const int64_t n = d.old.k_tiles * TILE + d.n_cand;
+    if (n <= 0) return hipSuccess;
+    if (n >= (int64_t)0xFFFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pc_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d, elems[0]);
+    // stable LSD passes over the key (bits 32 and up of an element), 8 bits each: the elements
+    // are listed by source, so equal keys keep the rule's order (old position, then C index)
+    NoVal* nv = nullptr;
+    const RegionSink none{};
+    for (int b = 0; b < std::max(key_bits, 1); b += 8) {
+        const hipError_t e = rs_pass<uint64_t, NoVal, 8>(elems[*sorted], nv, elems[*sorted ^ 1], nv, n, 32 + b, hist, tot,
+                                                         none, st);
+        if (e != hipSuccess) return e;
+        *sorted ^= 1;
+    }
     return hipGetLastError();
 }
 

@@ -61,6 +61,10 @@ esc_ctx* multi_sub(const esc_ctx* c, int i);                                    
 int32_t multi_k1_calibrate(esc_ctx* c, int32_t rounds);
 int32_t multi_pods_upsert(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p);
 int32_t multi_pods_grow(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p);
+int32_t multi_pods_compact(esc_ctx* c, void* jobs, int32_t (*build)(esc_ctx*, int, void*),
+                           int32_t (*commit)(esc_ctx*, int, void*));
+int32_t multi_pods_slack(const esc_ctx* c, int64_t* k_tiles, int64_t* k_tiles_rule, int64_t* parked);
+int32_t multi_pod_where(const esc_ctx* c, int64_t id, int32_t* class_id, int64_t* pos);
 int32_t multi_pods_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_pods_bind(esc_ctx* c, const int64_t* ids, const uint32_t* pod_node, int64_t n);
 int32_t multi_nodes_update(esc_ctx* c, const int64_t* ids, int64_t n, const uint32_t* flags, const int64_t* cpu,

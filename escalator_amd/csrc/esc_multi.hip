@@ -397,6 +397,39 @@ int32_t multi_pods_grow(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) {
     return ESC_OK;
 }
 
+// esc_pods_compact: every device's new K section is built and checked (build) before any device
+// swaps (commit); the two halves and their per-device jobs are esc_pod_compact.hip's.
+int32_t multi_pods_compact(esc_ctx* c, void* jobs, int32_t (*build)(esc_ctx*, int, void*),
+                           int32_t (*commit)(esc_ctx*, int, void*)) {
+    if (M(c).pod_lo.empty() || M(c).diverged) return ESC_E_STATE;
+    for (int s = 0; s < nsub(c); ++s)
+        if (int32_t rc = build(M(c).subs[s], s, jobs)) return rc;
+    for (int s = 0; s < nsub(c); ++s)
+        if (int32_t rc = commit(M(c).subs[s], s, jobs)) return rc;
+    return ESC_OK;
+}
+
+int32_t multi_pods_slack(const esc_ctx* c, int64_t* k_tiles, int64_t* k_tiles_rule, int64_t* parked) {
+    int64_t a = 0, b = 0, d = 0;
+    for (int s = 0; s < nsub(c); ++s) {
+        int64_t x = 0, y = 0, z = 0;
+        if (int32_t rc = esc_pods_slack(M(c).subs[s], &x, &y, &z)) return rc;
+        a += x; b += y; d += z;
+    }
+    if (k_tiles) *k_tiles = a;
+    if (k_tiles_rule) *k_tiles_rule = b;
+    if (parked) *parked = d;
+    return ESC_OK;
+}
+
+// The pod's class and position inside its own device's shard.
+int32_t multi_pod_where(const esc_ctx* c, int64_t id, int32_t* class_id, int64_t* pos) {
+    if (id < 0) return ESC_E_INVAL;
+    if (M(c).pod_lo.empty()) return ESC_E_STATE;
+    const int s = owner_of_pod(c, id);
+    return esc_pod_where(M(c).subs[s], id - M(c).pod_lo[s], class_id, pos);
+}
+
 int32_t multi_pods_upsert(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) {
     const int k = nsub(c);
     std::vector<PodBatch> b;

@@ -35,38 +35,8 @@ static_assert(CS_SLOTS * CS_REC <= 128 && CS_SLOTS * CS_XP <= 128, "a spare C ti
 constexpr uint32_t CS_FLAGS = ESC_PF_DAEMONSET | ESC_PF_HAS_OVH | (uint32_t)CS_XREG << ESC_PF_XREG_SHIFT |
                               (uint32_t)CS_XINIT << ESC_PF_XINIT_SHIFT | (uint32_t)CS_XP << ESC_PF_XPAIR_SHIFT;
 
-// Can no group ever count the pod, whatever the groups' state?  A daemonset pod is excluded
-// by both filters (node_group.go:221, :259); a pod that blocks the default filter (static, a
-// selector, a blocking affinity) joins only the slots of its pairs, so it is inert when none
-// of them is a group pair (< n_gp).  A pod that does not block the default filter joins the
-// default slot and is never inert.  (escalator_amd/layout.py inert_mask restates it.)
-inline bool pod_inert(uint32_t f, uint32_t pair0, const uint32_t* xp, uint32_t n_gp) {
-    if (f & ESC_PF_DAEMONSET) return true;
-    if (!(f & (ESC_PF_STATIC | ESC_PF_HAS_SEL | ESC_PF_AFF_BLOCK))) return false;
-    if (pair0 < n_gp) return false;
-    for (uint32_t k = 0, np = pf_xpair(f); k < np; ++k)
-        if (xp[k] < n_gp) return false;
-    return true;
-}
-
-// K class of a pod, the one place that decides it: -1 for the C section (more
-// than 3 extra container records or more than 3 extra pairs); else the fold (kp_fold) either
-// packs the pod's effective request — class id = its pair count np | packed << 7, packed 2
-// for the packed small block and 1 for the packed block, a signature without records — or
-// leaves the pod its records in the plain class of its own signature.  xc_cpu / xc_mem: the
-// pod's own records (null when it has none).  xp: its extra pairs (null when it has none).  A
-// pod of the packed small block that is inert (pod_inert) takes the inert class of its pair
-// count instead, id np | 3 << 7: the same tile, kept out of K1's stream.
-inline int pod_class_id(uint32_t f, uint32_t cpu0, int64_t mem0, uint32_t pair0, const int64_t* xc_cpu,
-                        const int64_t* xc_mem, const uint32_t* xp, uint32_t n_gp) {
-    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, np = pf_xpair(f);
-    if (xr + xi + ov > 3 || np > 3) return -1;
-    int64_t cpu, mem;
-    const uint32_t packed = kp_fold(f, cpu0, mem0, pair0, xc_cpu, xc_mem, n_gp, cpu, mem);
-    if (packed == 2 && pod_inert(f, pair0, xp, n_gp)) return (int)(np | POD_INERT_ID0);
-    if (packed) return (int)(np | packed * POD_SIG_IDS);
-    return (int)(((xr * 4 + xi) * 2 + ov) * 4 + np);
-}
+// (pod_inert and pod_class_id, the one definition of a pod's class, are in esc_kblock.h: the
+// device classifies re-homed pods by the same body, esc_pods_compact.)
 
 // Does C slot room `cf` (counts of a slot's flags) hold a pod with flags f?  Its records
 // and pairs take the slot's first positions of each kind, the rest stay neutral.
@@ -257,6 +227,101 @@ inline int32_t plan_pod_grow(PodGrowPlan& P, const PodGrowIn& in) {
             P.xc_base.push_back((uint32_t)(in.xc_end + (uint64_t)(t + 1) * CS_SLOTS * CS_REC));
             P.xp_base.push_back((uint32_t)(in.xp_end + (uint64_t)(t + 1) * CS_SLOTS * CS_XP));
         }
+    }
+    return ESC_OK;
+}
+
+// ---- esc_pods_compact
+// The bucket of a pod inside its class (esc_load_pods' step 4): pair0 / pod_sort, NONE and the
+// pairs no group selects last; one bucket when pod_sort == 0.
+inline int64_t pod_buckets(uint32_t pod_sort, uint32_t n_gp) { return pod_sort ? (int64_t)(n_gp / pod_sort) + 2 : 1; }
+inline int64_t pod_bucket(uint32_t pair0, uint32_t pod_sort, uint32_t n_gp) {
+    return pod_sort ? (pair0 < n_gp ? (int64_t)(pair0 / pod_sort) : pod_buckets(pod_sort, n_gp) - 1) : 0;
+}
+// Is the C slot with flags cf live and its pod K-holdable by the host's counts (h_cused: the
+// pod's own records | pairs << 16)?  A slot whose flags are the daemonset bit alone is padding.
+inline bool c_slot_parked(uint32_t cf, uint32_t used) { return cf != ESC_PF_DAEMONSET && (used & 0xFFFF) <= 3 && (used >> 16) <= 3; }
+// The flags a re-homed pod leaves behind in its C slot, as esc_pods_delete leaves them: free
+// (daemonset-flagged), the counts kept as the slot's room.
+inline uint32_t c_slot_freed(uint32_t cf) { return cf | ESC_PF_DAEMONSET; }
+
+// What esc_pods_compact knows before it plans: the resident classes, their free positions and
+// the re-homed pods by class id (the device's classification of the K-holdable C slots).
+struct PodCompactIn {
+    const std::vector<PodClass>* cls = nullptr;
+    const std::vector<int>* cls_of = nullptr;     // [POD_CLASS_IDS] class id -> class index, -1: none
+    const int64_t* k_free = nullptr;              // [classes] free positions
+    const int64_t* arr = nullptr;                 // [POD_CLASS_IDS] re-homed pods, by class id
+    double f = 0;                                 // esc_set_spare
+    int64_t c_tiles = 0;                          // C tiles resident (they stay)
+};
+
+struct PodCompactPlan {
+    // the new class table: old indices kept, created classes behind them in ascending class id
+    std::vector<PodClass> cls;
+    std::vector<int> cls_of;
+    std::vector<int64_t> live;                    // [classes] live pods after the re-homing
+    std::vector<PcCls> tab;                       // [classes] k_pc_move's table
+    std::vector<uint32_t> tmpl;                   // the free tile of every class that has tiles
+    std::vector<std::pair<int64_t, int64_t>> k_free;   // [classes] the free positions [first, second)
+    int created = 0;
+    int64_t rehomed = 0;
+    int64_t k_tiles = 0, k_weight = 0, kb_words = 0;
+    int64_t tiles_before = 0, k1_bytes_before = 0, k1_bytes_after = 0;
+};
+
+// The plan (the rule of include/escalator_hip.h, esc_pods_compact): tiles_i = ceil((live_i +
+// s(live_i)) / 256) with the load's s; a class may shrink, grow or (f = 0) drop to no tile.
+// ESC_E_LIMIT when the pod slots leave 32 bits.
+inline int32_t plan_pod_compact(PodCompactPlan& P, const PodCompactIn& in) {
+    P = PodCompactPlan();
+    const std::vector<PodClass>& old = *in.cls;
+    P.cls = old;
+    P.cls_of = *in.cls_of;
+    const size_t n_old = old.size();
+    std::vector<int64_t> arr_cls(n_old, 0);
+    for (int id = 0; id < POD_CLASS_IDS; ++id) {
+        if (in.arr[id] <= 0) continue;
+        int ci = P.cls_of[id];
+        if (ci < 0) {
+            ci = P.cls_of[id] = (int)P.cls.size();
+            P.cls.push_back(pod_class_of_id(id));
+            arr_cls.push_back(0);
+            ++P.created;
+        }
+        arr_cls[ci] += in.arr[id];
+        P.rehomed += in.arr[id];
+    }
+    const size_t n = P.cls.size();
+    std::vector<int64_t> tiles(n);
+    P.live.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t was = i < n_old ? old[i].t1 - old[i].t0 : 0;
+        P.live[i] = (i < n_old ? was * TILE - in.k_free[i] : 0) + arr_cls[i];
+        tiles[i] = (P.live[i] + pod_spare(P.live[i], in.f) + TILE - 1) / TILE;
+        P.tiles_before += was;
+        if (i < n_old) P.k1_bytes_before += was * (int64_t)kb_k1_wt(old[i]) * 512;
+    }
+    P.k_tiles = cut_pod_classes(P.cls, tiles, P.kb_words, P.k_weight);
+    P.k1_bytes_after = P.k_weight * 512;
+    if (P.k_tiles * TILE + in.c_tiles * CTILE >= (int64_t)0xFFFFFFFF) return ESC_E_LIMIT;   // a PodRef's source slot
+    P.tab.resize(n);
+    P.k_free.resize(n);
+    int64_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const PodClass& k = P.cls[i];
+        PcCls m{};
+        m.start = at;
+        m.live = P.live[i];
+        m.tmpl = -1;
+        if (tiles[i] > 0) {
+            m.tmpl = (int64_t)P.tmpl.size();
+            P.tmpl.resize(P.tmpl.size() + (size_t)k.wt * KB_UNIT);
+            write_free_tile(k, P.tmpl.data() + m.tmpl);
+        }
+        at += P.live[i];
+        P.tab[i] = m;
+        P.k_free[i] = {P.live[i], tiles[i] * TILE};
     }
     return ESC_OK;
 }

@@ -3271,6 +3271,10 @@ int32_t batch_shape(const esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, 
     }
     return ESC_OK;
 }
+int32_t refresh_podrefs(esc_ctx* c, std::vector<int64_t>& ids) {
+    std::vector<uint32_t> runs;
+    return sync_placement(c, ids, runs);
+}
 int32_t pods_upsert_check(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p) {
     UpsertPlan u;
     return upsert_plan(c, ids, p, u);

@@ -13,7 +13,10 @@ re-derived on the device, no pod reloaded) and retried once.  With ``compact=Tru
 and retried once; the queue's index maps follow the returned map.  With ``pod_grow=True`` a
 ``pods_upsert`` that answers ``ESC_E_LIMIT`` (more pods than the load left room for) is answered
 by one ``pods_grow`` with the same ids and packed batch (the pod classes grown on the device, no
-pod reloaded, every id kept) and one retry; a second limit reloads.
+pod reloaded, every id kept) and one retry; a second limit reloads.  With ``pod_compact=frac`` a
+flush that applied cleanly is followed by one ``pods_compact`` (the pod side re-laid on the device:
+classes shrunk to the load's rule, parked pods back in their classes, every id kept) when
+``pods_slack`` reports ``(k_tiles - k_tiles_rule) * 256 + parked >= frac * live pods``.
 
 It holds the current objects (plain-dict records, escalator_amd/objects.py) — the truth a
 reload is built from — and, beside them, what the device last saw of each.  Ingest
@@ -26,10 +29,11 @@ queue holds.  ``ctx`` is anything with ``Context``'s methods.
 from __future__ import annotations
 
 import heapq
+import logging
 
 import numpy as np
 
-from ._lib import ESC_E_LIMIT
+from ._lib import ESC_E_LIMIT, ESC_E_STATE
 from .objects import NO_DELETE_ANNOTATION, TO_BE_REMOVED_KEY, placement, taint_time
 
 NONE = 0xFFFFFFFF
@@ -73,7 +77,8 @@ def _status(n: dict):
 
 
 class EventQueue:
-    def __init__(self, spare: float = 0.5, rebuild: bool = False, compact: bool = False, pod_grow: bool = False):
+    def __init__(self, spare: float = 0.5, rebuild: bool = False, compact: bool = False, pod_grow: bool = False,
+                 pod_compact: float | None = None):
         self.spare = float(spare)
         self.compact = bool(compact)               # answer a lack of table slots / a full run with nodes_compact
         self.rebuild = bool(rebuild) or self.compact   # answer a node-side ESC_E_LIMIT with nodes_rebuild first
@@ -84,6 +89,11 @@ class EventQueue:
         self.pod_grow = bool(pod_grow)             # answer a full pod class / C section with pods_grow
         self.pod_grows = 0
         self.pod_grow_causes: list[str] = []       # the call that answered ESC_E_LIMIT
+        # re-lay the pod side (pods_compact) once its slack reaches this fraction of the live pods
+        self.pod_compact = None if pod_compact is None else float(pod_compact)
+        self.pod_compacts = 0
+        self.pod_compact_causes: list[str] = []    # "slack" (free tiles alone reach the threshold) / "parked"
+        self.pod_compact_failures = 0
         self.pods: dict[str, dict] = {}            # the object store: key -> pod, name -> node
         self.nodes: dict[str, dict] = {}           # (insertion order = arrival order)
         self._dev_pods: dict[str, dict] = {}       # the records the device holds, as last flushed
@@ -243,7 +253,41 @@ class EventQueue:
             self._apply(ctx, dirty_p, dirty_n)
         except _Reload as e:
             self.reload_causes.append(str(e))
-            self._reload(ctx, dirty_p, dirty_n)
+            return self._reload(ctx, dirty_p, dirty_n)
+        if self.pod_compact is not None:
+            self._maybe_compact_pods(ctx)
+
+    def _maybe_compact_pods(self, ctx):
+        """After a flush that applied cleanly: one ``pods_compact`` when the free tiles beyond
+        the load's rule and the parked pods together reach ``pod_compact`` of the live pods.  A
+        compaction that fails before its swap changed nothing: logged, counted and ignored.
+        One that fails after it leaves the context stale (``pods_slack`` then answers
+        ESC_E_STATE): the snapshot is reloaded at once, cause ``"pods_compact"``."""
+        s = ctx.pods_slack()
+        tiles = (s["k_tiles"] - s["k_tiles_rule"]) * 256
+        need = self.pod_compact * len(self._pod_id)
+        if tiles + s["parked"] <= 0 or tiles + s["parked"] < need:
+            return
+        try:
+            ctx.pods_compact()
+        except Exception as e:
+            if getattr(e, "code", None) is None:
+                raise
+            self.pod_compact_failures += 1
+            log = logging.getLogger(__name__)
+            try:
+                ctx.pods_slack()
+            except Exception as e2:
+                if getattr(e2, "code", None) != ESC_E_STATE:
+                    raise
+                log.warning("pods_compact failed after its swap (%s): the snapshot is stale and is reloaded", e)
+                self.reload_causes.append("pods_compact")
+                self._reload(ctx, {}, {})
+                return
+            log.warning("pods_compact failed before its swap (%s): the snapshot stays as it is", e)
+            return
+        self.pod_compacts += 1
+        self.pod_compact_causes.append("slack" if tiles > 0 and tiles >= need else "parked")
 
     def reload(self, ctx, cause: str):
         """One full load from the object store outside a flush (a failed audit): `cause` goes

@@ -168,6 +168,54 @@ def pod_bytes(pods: dict, n_gp: int, lo: int = 0, hi: int | None = None) -> int:
     return int(plain + packed + small + c_tiles * 8)
 
 
+POD_SORT = 32             # esc_ctx.h pod_sort: one K3 column of pod slots per bucket
+POD_INERT_ID0 = 3 * 128
+
+
+def class_ids(pods: dict, n_gp: int) -> np.ndarray:
+    """Every pod's class id (esc_kblock.h pod_class_id): -1 the C section (more than 3 extra
+    records or pairs), else pairs | 2 << 7 the packed small class, pairs | 3 << 7 its inert
+    class, pairs | 1 << 7 the packed class, else the plain class of the pod's signature,
+    ((regular * 4 + init) * 2 + overhead) * 4 + pairs."""
+    f = np.asarray(pods["flags"], np.uint64)
+    nreg, ninit, ovh = ((f >> 8) & 0xFF).astype(np.int64), ((f >> 16) & 0xFF).astype(np.int64), ((f >> 4) & 1).astype(np.int64)
+    nxp = ((f >> 24) & 0x3F).astype(np.int64)
+    fold = folded_request(pods)
+    pk, sm = packed_mask(pods, fold), small_mask(pods, n_gp, fold)
+    inert = inert_mask(pods, n_gp)
+    out = ((nreg * 4 + ninit) * 2 + ovh) * 4 + nxp
+    out = np.where(pk, nxp | (1 << 7), out)
+    out = np.where(sm, nxp | (2 << 7), out)
+    out = np.where(sm & inert, nxp | POD_INERT_ID0, out)
+    return np.where((nreg + ninit + ovh > 3) | (nxp > 3), -1, out)
+
+
+def compact_positions(cls, src, pair0, live, rehomed, n_gp: int, pod_sort: int = POD_SORT) -> np.ndarray:
+    """The order rule of esc_pods_compact over one entry per pod: ``cls`` the class the pod
+    is in afterwards (any integer label; < 0: the pod stays in the C section), ``src`` its old
+    position inside the class, or the C-array index of a re-homed pod (``rehomed``), ``pair0``
+    its first pair and ``live`` whether the entry holds a pod at all.  Inside a class the live
+    pods take positions 0, 1, ... by ascending bucket (pair0 < n_gp ? pair0 // pod_sort : last;
+    one bucket when pod_sort is 0), inside a bucket the resident pods by ascending old
+    position, then the re-homed pods by ascending C-array index.  Returns each entry's
+    position, -1 for the others."""
+    cls, src = np.asarray(cls, np.int64), np.asarray(src, np.int64)
+    pair0 = np.asarray(pair0, np.uint32).astype(np.int64)
+    ok = np.asarray(live, bool) & (cls >= 0)
+    rehomed = np.asarray(rehomed, bool)
+    last = n_gp // pod_sort + 1 if pod_sort else 0
+    bucket = np.where(pair0 < n_gp, pair0 // pod_sort, last) if pod_sort else np.zeros(len(cls), np.int64)
+    order = np.lexsort((src, rehomed, bucket, cls))
+    order = order[ok[order]]
+    pos = np.full(len(cls), -1, np.int64)
+    c = cls[order]
+    first = np.r_[0, np.flatnonzero(c[1:] != c[:-1]) + 1] if len(c) else np.zeros(0, np.int64)
+    start = np.zeros(len(c), np.int64)
+    start[first] = first
+    pos[order] = np.arange(len(c)) - np.maximum.accumulate(start)
+    return pos
+
+
 def node_entries(nodes: dict) -> np.ndarray:
     """Label pair of every (pair, node) entry, in entry (pair-sorted) order."""
     label0 = np.asarray(nodes["label0"], np.uint32)

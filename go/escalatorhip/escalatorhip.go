@@ -720,6 +720,38 @@ func (x *Context) PodsRoom() (kCapacity, kFree, cFree int64, perClass []int64, e
 	return int64(a), int64(b), int64(d), perClass, err
 }
 
+// PodsCompactReport is what PodsCompact did (esc_pods_compact_report).
+type PodsCompactReport struct {
+	Rehomed        int64 // pods that left the C section
+	ClassesCreated int64 // classes appended for them
+	KTilesBefore   int64
+	KTilesAfter    int64
+	K1BytesBefore  int64 // K-block bytes the pod pass streams per decision
+	K1BytesAfter   int64
+	Moved          int64 // pods whose position changed
+	CFreeBefore    int64 // free C slots
+	CFreeAfter     int64
+}
+
+// PodsCompact re-lays the pod side on the device (esc_pods_compact): pods parked in C slots go
+// back to their classes, every class is re-cut to the load's rule over its live pods and its
+// pods re-sorted by column bucket.  No pod is reloaded; every id, the placement and the node
+// side stay.  The loop calls it when PodsSlack says enough room or parked pods have piled up.
+func (x *Context) PodsCompact() (PodsCompactReport, error) {
+	var r C.esc_pods_compact_report
+	err := rcErr("esc_pods_compact", C.esc_pods_compact(x.c, &r))
+	return PodsCompactReport{int64(r.rehomed), int64(r.classes_created), int64(r.k_tiles_before), int64(r.k_tiles_after),
+		int64(r.k1_bytes_before), int64(r.k1_bytes_after), int64(r.moved), int64(r.c_free_before), int64(r.c_free_after)}, err
+}
+
+// PodsSlack returns the K tiles resident, the tiles the load's rule cuts for the present live
+// counts and the live pods in C slots that a K class could hold (esc_pods_slack; host only).
+func (x *Context) PodsSlack() (kTiles, kTilesRule, parked int64, err error) {
+	var a, b, d C.int64_t
+	err = rcErr("esc_pods_slack", C.esc_pods_slack(x.c, &a, &b, &d))
+	return int64(a), int64(b), int64(d), err
+}
+
 // PodsDelete removes pods by snapshot index.
 func (x *Context) PodsDelete(ids []int64) error {
 	return rcErr("esc_pods_delete", C.esc_pods_delete(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), C.int64_t(len(ids))))

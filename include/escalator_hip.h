@@ -551,6 +551,61 @@ int32_t esc_pods_delete(esc_ctx* ctx, const int64_t* ids, int64_t n);
 int32_t esc_pods_grow(esc_ctx* ctx, const int64_t* ids, const esc_pod_soa* pods);
 int32_t esc_pods_room(const esc_ctx* ctx, int64_t* k_capacity, int64_t* k_free, int64_t* c_free,
                       int64_t* per_class /* [512] or NULL */);
+/* The pod side after bursts, deletes and parked pods.  esc_pods_compact re-lays it on the device:
+ * no pod is re-uploaded and no pod id changes; when it returns the K section is what
+ * esc_load_pods would have cut for the live pods at the context's spare fraction, except that
+ * the order of pods inside a column bucket is the rule below and not the load's input order.
+ *   Re-home.  Every live pod in a C slot whose present shape has at most 3 extra container
+ *   records and at most 3 extra pairs leaves the C section.  Its shape is read on the device from
+ *   the slot: its pairs are the first ones (the host knows how many), its records the first of
+ *   each kind in the slot's room up to the last that is not neutral.  A regular container or an
+ *   overhead that requests (0, 0), and an init container without both keys, equal the neutral
+ *   record and are read as absent: they add nothing to any sum, but such a pod that keeps its
+ *   records (a plain class) takes the class without them, so for it alone the layout,
+ *   esc_stream_bytes and esc_pods_room can differ from what esc_load_pods would give.  The
+ *   class is decided on the device by the definition the
+ *   load and esc_pods_upsert use; it is written into the class as an upsert would write it
+ *   (folded for the packed classes, records kept in a plain class, the inert class where no group
+ *   can count it).  The vacated slot becomes a free C slot as esc_pods_delete leaves one (the
+ *   daemonset flag set, the counts kept as its room, records neutral, pairs ESC_NONE).  A class
+ *   the context lacks is appended behind the existing ones in ascending class id; class indices
+ *   of the other classes stay.  C tiles are never removed and pods that need a C slot stay.
+ *   Re-cut.  For class i with live_i pods after the re-homing,
+ *     tiles_i = ceil((live_i + s(live_i)) / 256),  s(x) = f > 0 ? max(1, floor(x * f)) : 0:
+ *   a class may shrink, grow, or (f = 0) drop to no tile; it keeps its index.
+ *   Re-sort.  Inside a class the live pods take positions [0, live_i): ascending bucket
+ *   (pair0 < group pairs ? pair0 / 32 : last), inside a bucket the resident pods by ascending
+ *   old position, then the re-homed pods by ascending C-array index.  The other positions are
+ *   free.  The order is a function of the snapshot before the call alone.
+ * Kept: pod ids, the placement and the occupancy words, the node side, the age index,
+ * esc_set_state, the tracker, the K1 calibration when the grid did not change.  Invalidated, as
+ * after esc_pods_grow: captured graphs, the last decision's records, selections and
+ * esc_try_remove results.  esc_stream_bytes counts a re-homed pod as a pod of its class from
+ * then on.  All or nothing up to the swap of the new K array: ESC_E_LIMIT (offsets past 32
+ * bits), ESC_E_NOMEM / ESC_E_HIP leave the snapshot as it was; a failure after the swap leaves
+ * the context stale until esc_load_pods.  ESC_E_STATE before esc_load_pods or on a stale
+ * context, ESC_E_NODEV without a device.  Multi-device: every device's new K section is built
+ * and checked before any device swaps; the ranks of a sharded job each compact their own shard
+ * (no collective).  Peak extra device memory: the new K array, 20 B per old K position (the
+ * map and the sort's two element arrays) and one free tile per class.
+ * esc_pods_slack (host only; any pointer may be NULL): the K tiles resident, the tiles the rule
+ * above cuts for the present live counts (parked pods not counted in any class) and the live
+ * pods in C slots with at most 3 records and 3 pairs; ESC_E_STATE before esc_load_pods and on a
+ * context a failed pod event or a compaction that failed after its swap left stale, which is how
+ * a loop tells that failure from one before the swap.  esc_pod_where (host only): the pod's
+ * class id (-1: the C section, -2: absent) and its position inside the class, or its C-array
+ * index.                                                                                  */
+typedef struct esc_pods_compact_report {
+    int64_t rehomed;            /* pods that left the C section */
+    int64_t classes_created;
+    int64_t k_tiles_before, k_tiles_after;
+    int64_t k1_bytes_before, k1_bytes_after;   /* K-block bytes the pod pass streams per decision */
+    int64_t moved;              /* pods whose position changed (the re-homed ones included) */
+    int64_t c_free_before, c_free_after;       /* free C slots */
+} esc_pods_compact_report;
+int32_t esc_pods_compact(esc_ctx* ctx, esc_pods_compact_report* out /* may be NULL */);
+int32_t esc_pods_slack(const esc_ctx* ctx, int64_t* k_tiles, int64_t* k_tiles_rule, int64_t* parked);
+int32_t esc_pod_where(const esc_ctx* ctx, int64_t id, int32_t* class_id, int64_t* pos);
 int32_t esc_nodes_update(esc_ctx* ctx, const int64_t* ids, int64_t n, const uint32_t* flags,
                          const int64_t* cpu_m, const int64_t* mem_b);
 /* Node additions and deletions (the node informer's Add / Delete, pkg/k8s/cache.go:37-56)
