@@ -93,6 +93,13 @@ class AuditReport(C.Structure):
     _fields_ = [("ran", u32), ("skipped", u32), ("check", AuditCheck * len(AUDIT_CHECKS))]
 
 
+POD_AUDIT_CHECKS = ["MAP", "KSLOT", "CSLOT", "COUNT", "PODREF", "REPLICA"]   # ESC_PAUD_*
+
+
+class PodAuditReport(C.Structure):
+    _fields_ = [("ran", u32), ("skipped", u32), ("check", AuditCheck * len(POD_AUDIT_CHECKS))]
+
+
 PODS_COMPACT_FIELDS = ["rehomed", "classes_created", "k_tiles_before", "k_tiles_after", "k1_bytes_before",
                        "k1_bytes_after", "moved", "c_free_before", "c_free_after"]
 
@@ -222,6 +229,7 @@ _SIGS = {
     "esc_new_nodes_eval": (i32, [VP, P(i64), P(NewNodes)]),
     "esc_new_nodes_list": (i32, [VP, i32, P(i64), P(C.c_uint8), i64, P(i64)]),
     "esc_audit": (i32, [VP, u32, P(AuditReport)]),
+    "esc_audit_pods": (i32, [VP, u32, P(PodAuditReport)]),
     "esc_set_metrics": (i32, [VP, i32]),
     "esc_metrics_results": (i32, [VP, P(GroupMetrics)]),
     "esc_use_graph": (i32, [VP, i32]),

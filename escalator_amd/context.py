@@ -693,6 +693,23 @@ class Context:
         out["skipped"] = [n for k, n in enumerate(names) if (rep.skipped >> k) & 1]
         return out
 
+    def audit_pods(self, checks=None) -> dict:
+        """esc_audit_pods: the resident pod side (the id map, every K position and C slot, the
+        live counters, the PodRefs, the replicas) checked against itself and the host mirrors.
+        checks: names from ``_lib.POD_AUDIT_CHECKS`` (None = all).  Returns the shape of
+        ``audit()``; ``"skipped"`` holds PODREF without a placement and REPLICA with one replica."""
+        names = L.POD_AUDIT_CHECKS
+        mask = 0
+        for c in (checks or ()):
+            mask |= 1 << names.index(c)
+        rep = L.PodAuditReport()
+        L.check(self.lib.esc_audit_pods(self.handle, mask, C.byref(rep)), "esc_audit_pods")
+        out = {n: {"n_checked": int(rep.check[k].n_checked), "n_bad": int(rep.check[k].n_bad),
+                   "first_bad": int(rep.check[k].first_bad)}
+               for k, n in enumerate(names) if (rep.ran >> k) & 1}
+        out["skipped"] = [n for k, n in enumerate(names) if (rep.skipped >> k) & 1]
+        return out
+
     # ------------------------------------------------------------- ordering
     def sort_nodes(self):
         L.check(self.lib.esc_sort_nodes(self.handle), "esc_sort_nodes")

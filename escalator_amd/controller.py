@@ -460,6 +460,11 @@ class ResidentController(Controller):
     reloads the snapshot once from the queue's object store (``events.reload_causes`` gets
     ``"audit:<check>"``) and counts in ``audit_failures``; ``audits`` counts the passes.
 
+    ``pod_audit_every=k`` (keyword-only, 0 = never): the same schedule for ``ctx.audit_pods()``,
+    the pod side's audit, after ``audit_every``'s pass when both fall on a scan; a mismatch reloads
+    once (``"pod_audit:<check>"``); counters ``pod_audits``, ``pod_audit_failures``,
+    ``last_pod_audit``.
+
     ``node_rebuild=True``: a ``nodes_add`` / ``nodes_relabel`` that runs out of node-side spare
     room is answered by ``ctx.nodes_rebuild()`` and one retry before any reload
     (``events.rebuild_causes``), and so is an audit mismatch confined to the state a rebuild
@@ -484,10 +489,13 @@ class ResidentController(Controller):
     (``events.pod_compacts`` / ``events.pod_compact_causes``).  Pod ids and the placement stay."""
 
     REBUILT_CHECKS = ("ENTRY", "FIRST", "REGION", "OCC", "TRACKER")
+    # the pod audit is off unless the constructor's keyword turns it on
+    pod_audit_every, pod_audits, pod_audit_failures, last_pod_audit = 0, 0, 0, None
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
                  selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0, node_rebuild: bool = False,
-                 node_compact: bool = False, pod_grow: bool = False, *, pod_compact: float | None = None):
+                 node_compact: bool = False, pod_grow: bool = False, *, pod_compact: float | None = None,
+                 pod_audit_every: int = 0):
         super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
                          selection_slack=selection_slack)
         from .events import EventQueue
@@ -505,6 +513,12 @@ class ResidentController(Controller):
         self.audits = 0
         self.audit_failures = 0
         self.last_audit = None
+        # the pod side's resync: every pod_audit_every-th scan runs ctx.audit_pods() after the
+        # flush (and after audit_every's pass when both fall on a scan); 0 = never
+        self.pod_audit_every = int(pod_audit_every)
+        self.pod_audits = 0
+        self.pod_audit_failures = 0
+        self.last_pod_audit = None
 
     def _learned(self, name: str, j: int, t: int):
         """The queue keeps the cache: it drops a name on node_delete and re-sends the cache
@@ -539,11 +553,23 @@ class ResidentController(Controller):
                     return
             self.events.reload(self.ctx, "audit:" + bad[0])
 
+    def _pod_audit(self):
+        """Context.audit_pods on the flushed snapshot; a mismatch reloads once (cause
+        "pod_audit:<the first failing check>"): nothing is repaired in place."""
+        self.last_pod_audit = rep = self.ctx.audit_pods()
+        self.pod_audits += 1
+        bad = [n for n in L.POD_AUDIT_CHECKS if n in rep and rep[n]["n_bad"] > 0]
+        if bad:
+            self.pod_audit_failures += 1
+            self.events.reload(self.ctx, "pod_audit:" + bad[0])
+
     def run_once(self) -> list[dict]:
         self.events.flush(self.ctx)
         self.scans += 1
         if self.audit_every and self.scans % self.audit_every == 0:
             self._audit()
+        if self.pod_audit_every and self.scans % self.pod_audit_every == 0:
+            self._pod_audit()
         if self.events.touched_nodes:
             self._sync_trackers()
         now = self.clock()

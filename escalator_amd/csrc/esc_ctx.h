@@ -5,6 +5,7 @@
 //   esc_pod_grow.hip  the pod classes grown on the device (esc_pods_grow, esc_pods_room)
 //   esc_pod_compact.hip  the pod side re-laid on the device (esc_pods_compact, esc_pods_slack,
 //                     esc_pod_where)
+//   esc_pod_audit.hip  the pod side's read-only audit (esc_audit_pods)
 // Everything else (esc_multi.hip, esc_list.hip, the packer, the generator) sees esc_ctx as
 // opaque.  Helpers that cross a file are declared at the end, each defined in the file of its
 // subsystem; the small ones are inline here.
@@ -344,6 +345,8 @@ struct esc_ctx {
     esc::RmRec* h_rm = nullptr;                               // K7 results (pinned copy)
     uint8_t* h_istage = nullptr;                              // age-index build uploads (pinned)
     size_t istage_cap = 0;
+    uint8_t* h_pstage = nullptr;                              // esc_audit_pods' staging (pinned; two halves + the
+    hipEvent_t pstage_ev[2] = {};                             // report), made at the first call; a half's last use
     int64_t* h_words = nullptr;                               // esc_results' pod + node words (pinned)
     size_t words_cap = 0;
     // Small contexts (G <= HTOT_MAX_GROUPS): K4 writes every decided group's totals record

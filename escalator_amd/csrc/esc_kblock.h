@@ -353,4 +353,42 @@ struct CPodRec {                       // its records (regular, init, overhead s
 static_assert(sizeof(CPodRec) == 64, "one LDS row per lane");
 constexpr uint32_t K_TILE_WEIGHT_MAX = k_tile_weight(3, 3);   // the heaviest tile (plain, 3 records, 3 pairs)
 
+// esc_audit_pods.  The class id (pod_class_id's numbering) of the pods a class
+// holds, from the class's own fields; -1 for fields no class can have.
+ESC_KB_HD int kb_class_id(const PodClass& C) {
+    if (C.packed > 2 || C.nxp > 3 || C.xreg > 3 || C.xinit > 3 || C.ovh > 1 || kb_nrec(C) > 3) return -1;
+    if (C.packed && kb_nrec(C)) return -1;
+    if (kb_inert(C)) return C.packed == 2 ? (int)(C.nxp | POD_INERT_ID0) : -1;
+    if (C.packed) return (int)(C.nxp | C.packed * POD_SIG_IDS);
+    return (int)(((C.xreg * 4 + C.xinit) * 2 + C.ovh) * 4 + C.nxp);
+}
+// The class id the stored words of K pod s of the block at word blk re-derive to: the words
+// read back as every reader reads them (kb_head, kb_rec, kb_pair) and classified by the one rule
+// (pod_class_id) in a context of n_gp group pairs.  For a pod that kb_write_pod wrote into a
+// class the rule chose this is that class's id (kb_class_id): a packed pod reads back as one
+// container with its folded request, which folds to itself; a plain pod reads back whole.  A
+// slot of a free tile (kb_write_free over zeroes) re-derives to the inert class of the tile's
+// pair count where the context has packed small classes (n_gp < KP8_PAIR_NONE), else to the
+// packed class of that count: never to a plain class, and to a packed or packed small class
+// only as said.  Where it re-derives to its own class (an inert class; a packed class without
+// packed small ones) a free slot and a live daemonset pod of zero request are the same words,
+// and a freed plain slot keeps its pod's other words, so the free lists, not this function,
+// say which slot is free.
+// r: one CPodRec of scratch (a lane's LDS row on the
+// device, so that the rule's loops index memory).  The class must be a holdable one
+// (kb_class_id(C) >= 0) and the block inside the array: the caller checks both.
+ESC_KB_HD int kb_pod_class(const PodClass& C, const uint32_t* kb, int64_t blk, int64_t s, uint32_t n_gp, CPodRec& r) {
+    const KHead h = kb_head(C, kb, blk, s);
+    const uint32_t R = C.packed ? 0u : kb_nrec(C);
+    for (uint32_t k = 0; k < 3; ++k) {
+        r.xc[k] = r.xm[k] = 0;
+        if (k < R) kb_rec(C, kb, blk, k, s, r.xc[k], r.xm[k]);
+        r.xp[k] = k < C.nxp ? kb_pair(C, kb, blk, k, s) : NONE;
+    }
+    // a plain pod's stored flags carry its own counts; more than the class's rows hold is read
+    // as a class no tile has, never as a longer record list
+    if (!C.packed && (pf_xctr(h.flags) != R || pf_xpair(h.flags) != C.nxp)) return -1;
+    return pod_class_id(h.flags, (uint32_t)h.cpu0, h.mem0, h.pair0, r.xc, r.xm, r.xp, n_gp);
+}
+
 }  // namespace esc

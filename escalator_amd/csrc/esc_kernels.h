@@ -345,6 +345,44 @@ hipError_t launch_audit_occ(const NodeDev& n, const GroupDev& g, const AuditDev&
 // TRACKER: one thread per node slot and per tracker entry.
 hipError_t launch_audit_tracker(const NodeDev& n, const GroupDev& g, const AuditDev& a, hipStream_t st);
 
+// esc_audit_pods: the pod side's read-only checks.  `rep` is [ESC_PAUD_N][AW_K]
+// as esc_audit's; P is replica 0 (seg / wg_cols / wg_off unused).  Every offset derived from a
+// device word or a host mirror is compared with its array's size before it indexes.
+struct PodAuditDev {
+    PodDev P;
+    int64_t kb_words, n_xc, n_xp;      // sizes of P.kb (u32 words), P.xc_cpu / xc_mem, P.xp
+    int64_t n_slots;                   // k_tiles * 256 + c_tiles * 64 (a multiple of 32)
+    uint32_t* map_bits;                // [n_slots / 32] slots the id map names (zeroed by the host)
+    const uint32_t* free_bits;         // [n_slots / 32] slots the free lists name (+ C padding)
+    int64_t* rep;
+    uint32_t n_gp;
+};
+// MAP, part 1.  Pod ids [id0, id0 + n): their class index (-1 C, -2 absent) and position, the
+// host's class table (n_cls of them) for the tile ranges.
+hipError_t launch_paud_map(const PodAuditDev& a, const int32_t* cls, const int64_t* pos, int64_t id0, int64_t n,
+                           const PodClass* hcls, int32_t n_cls, hipStream_t st);
+// MAP, part 2: every slot in exactly one of the two bitmaps.
+hipError_t launch_paud_map_cmp(const PodAuditDev& a, hipStream_t st);
+// KSLOT: one workgroup per K tile.
+hipError_t launch_paud_kslot(const PodAuditDev& a, hipStream_t st);
+// CSLOT: one wave per C tile of [t0, t0 + nt); hflags / hused: the host's flags and counts of
+// those tiles' slots, hxc / hxp: the host's offsets [nt + 1] from tile t0.
+hipError_t launch_paud_cslot(const PodAuditDev& a, int64_t t0, int64_t nt, const uint32_t* hflags, const uint32_t* hused,
+                             const uint32_t* hxc, const uint32_t* hxp, hipStream_t st);
+// PODREF: run positions [r0, r0 + n), slot[i] the device slot of the pod bound there (NONE: no
+// pod); n_refs: PodRefs in refs.
+hipError_t launch_paud_podref(const PodAuditDev& a, const PodRef* refs, int64_t n_refs, const uint32_t* slot, int64_t r0,
+                              int64_t n, hipStream_t st);
+// n words of a device table against the host's copy of them; a difference at word i is reported
+// to `check` as ids[i / per] * mul when ids is given (the host's id of that row), else as i.
+hipError_t launch_paud_words(const PodAuditDev& a, int check, const uint32_t* dev, const uint32_t* host, int64_t n,
+                             const uint32_t* ids, int per, int64_t mul, hipStream_t st);
+// REPLICA: n_bytes of arrays x (replica 0) and y compared 16 B per lane, esz-byte elements
+// (4 or 8); code = replica << 56 | array << 48.  The check's n_checked grows by the elements
+// the kernel loaded and compared (n_bytes / esz).
+hipError_t launch_paud_replica(const PodAuditDev& a, const void* x, const void* y, int64_t n_bytes, int esz, int64_t code,
+                               hipStream_t st);
+
 
 // Ordering (K5), see esc_kernels.hip: the age index (once per snapshot) and the per-decision
 // (group, class) partition.

@@ -3862,7 +3862,321 @@ __global__ __launch_bounds__(256) void k_pc_cfree(PodCompactDev D, uint32_t* __r
     flags[d] = cf | ESC_PF_DAEMONSET;
 }
 
+// ===================================================================== pod audit (esc_audit_pods)
+// Read-only (PodAuditDev, esc_kernels.h).  The rule of the node audit holds: a
+// word under suspicion — a pod's position, a tile's class, an offset summed from C flags, a
+// slot — is compared with its array's size before it indexes; out of range is a mismatch.
+// Every kernel ends in audit_emit with all of its lanes.
+namespace {
+// Is class C (a tile's, by either table) one whose tile t lies inside the K blocks?
+__device__ __forceinline__ bool paud_tile_ok(const PodAuditDev& A, const PodClass& C, int64_t t) {
+    if (kb_class_id(C) < 0 || C.wt != k_tile_weight(kb_nrec(C), C.nxp, C.packed) || t < C.t0 || t >= C.t1 || C.kb0 < 0) return false;
+    const int64_t blk = kb_block(C, t);
+    return blk >= 0 && (blk & 3) == 0 && blk + (int64_t)C.wt * KB_UNIT <= A.kb_words;
+}
+__device__ __forceinline__ bool paud_bit(const uint32_t* bits, int64_t i) { return (bits[i >> 5] >> (i & 31)) & 1u; }
+}  // namespace
+
+// MAP, part 1.  One thread per pod id: a live id's class index and position are inside the host's
+// class table (C: inside the C arrays), and its slot's bit was not set before (atomic OR: the
+// id that finds it set is a duplicate, whichever of the two arrives second, reported by slot).
+__global__ __launch_bounds__(256) void k_paud_map(PodAuditDev A, const int32_t* __restrict__ cls,
+                                                  const int64_t* __restrict__ pos, int64_t id0, int64_t n,
+                                                  const PodClass* __restrict__ hcls, int32_t n_cls) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t chk = 0, bad = 0;
+    int64_t first = INT64_MAX;
+    if (i < n && cls[i] != -2) {
+        const int32_t ci = cls[i];
+        const int64_t q = pos[i], kslots = A.P.k_tiles * TILE;
+        int64_t slot = -1;
+        chk = 1;
+        if (ci == -1) {
+            if (q >= 0 && q < A.P.c_tiles * CTILE) slot = kslots + q;
+        } else if (ci >= 0 && ci < n_cls) {
+            const int64_t t0 = hcls[ci].t0, t1 = hcls[ci].t1;
+            if (t0 >= 0 && t1 <= A.P.k_tiles && q >= 0 && q < (t1 - t0) * TILE) slot = t0 * TILE + q;
+        }
+        if (slot < 0) {
+            bad = 1;
+            first = A.n_slots + id0 + i;
+        } else if (atomicOr(A.map_bits + (slot >> 5), 1u << (slot & 31)) & (1u << (slot & 31))) {
+            bad = 1;
+            first = slot;
+        }
+    }
+    audit_emit(A.rep, ESC_PAUD_MAP, chk, bad, first);
+}
+
+// MAP, part 2.  One thread per 32 slots: mapped XOR free holds for every slot.
+__global__ __launch_bounds__(256) void k_paud_map_cmp(PodAuditDev A) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0;
+    int64_t first = INT64_MAX;
+    if (w < A.n_slots / 32) {
+        const uint32_t x = ~(A.map_bits[w] ^ A.free_bits[w]);         // both or neither
+        if (x) {
+            bad = (uint32_t)__popc(x);
+            first = w * 32 + (__ffs((int)x) - 1);
+        }
+    }
+    audit_emit(A.rep, ESC_PAUD_MAP, 0, bad, first);
+}
+
+// KSLOT.  One 256-thread workgroup per K tile, one thread per slot, the read-back records and
+// pairs of a lane in its LDS row (k_pc_classify's staging).  The tile's class comes from the
+// device's table and is checked against the K blocks first: a tile no valid class covers is 256
+// mismatches and is not read.
+__global__ __launch_bounds__(256) void k_paud_kslot(PodAuditDev A) {
+    __shared__ CPodRec recs[256];
+    const int64_t t = blockIdx.x, s = threadIdx.x, slot = t * TILE + s;
+    const PodDev& P = A.P;
+    bool wrong = true;
+    if (P.n_cls > 0) {
+        const int ci = pc_tile_class(P.cls, P.n_cls, t);
+        const PodClass C = P.cls[ci];
+        if (paud_tile_ok(A, C, t)) {
+            const int64_t blk = kb_block(C, t);
+            if (paud_bit(A.free_bits, slot)) {
+                bool same = true;
+                const int64_t* kb64 = reinterpret_cast<const int64_t*>(P.kb);
+                const uint16_t* kb16 = reinterpret_cast<const uint16_t*>(P.kb);
+                kb_write_free(C, blk, s, [&](int width, int64_t at, uint64_t v) {
+                    const uint64_t have = width == 8 ? (uint64_t)kb64[at] : (width == 4 ? (uint64_t)P.kb[at] : (uint64_t)kb16[at]);
+                    same = same && have == v;
+                });
+                wrong = !same;
+            } else {
+                wrong = kb_pod_class(C, P.kb, blk, s, A.n_gp, recs[threadIdx.x]) != kb_class_id(C);
+            }
+        }
+    }
+    audit_emit(A.rep, ESC_PAUD_KSLOT, 1, wrong ? 1u : 0u, wrong ? slot : INT64_MAX);
+}
+
+// CSLOT.  One wave per 64-slot C tile, one lane per slot; the slots' record and pair offsets by
+// a wave prefix sum of the device flags' counts from the HOST's tile offsets (checked by the
+// host to ascend inside the arrays), so a room is read only where it lies inside its tile.
+__global__ __launch_bounds__(256) void k_paud_cslot(PodAuditDev A, int64_t t0, int64_t nt,
+                                                    const uint32_t* __restrict__ hflags, const uint32_t* __restrict__ hused,
+                                                    const uint32_t* __restrict__ hxc, const uint32_t* __restrict__ hxp) {
+    const PodDev& P = A.P;
+    const int lane = threadIdx.x & 63;
+    const int64_t lt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    uint32_t chk = 0, bad = 0;
+    int64_t first = INT64_MAX;
+    if (lt < nt) {                                           // (wave-uniform)
+        const int64_t t = t0 + lt, d = t * CTILE + lane;
+        const uint32_t cf = P.flags[d], hf = hflags[lt * CTILE + lane], used = hused[lt * CTILE + lane];
+        const uint32_t cr = pf_xreg(cf), ci = pf_xinit(cf), cv = (cf & ESC_PF_HAS_OVH) ? 1u : 0u, cp = pf_xpair(cf);
+        const uint32_t nrec = cr + ci + cv;
+        const int64_t ro = (int64_t)hxc[lt] + (wave_incl_scan32(nrec) - nrec), po = (int64_t)hxp[lt] + (wave_incl_scan32(cp) - cp);
+        const int64_t r_end = imin64((int64_t)hxc[lt + 1], A.n_xc), p_end = imin64((int64_t)hxp[lt + 1], A.n_xp);
+        const bool is_free = paud_bit(A.free_bits, P.k_tiles * TILE + d);
+        bool wrong = cf != hf;
+        if (lane == 0) wrong |= P.xc_base[t] != hxc[lt] || P.xp_base[t] != hxp[lt];
+        if (lane == 63 && t + 1 == P.c_tiles) wrong |= P.xc_base[t + 1] != hxc[lt + 1] || P.xp_base[t + 1] != hxp[lt + 1];
+        if (ro + nrec > r_end || po + cp > p_end) {
+            wrong = true;                                    // the room leaves its tile: not read
+        } else if (is_free) {
+            wrong |= !(cf & ESC_PF_DAEMONSET);
+        } else {
+            const uint32_t np = used >> 16;
+            uint32_t xr = 0, xi = 0, ov = 0;
+            for (uint32_t k = 0; k < cr; ++k)
+                if (P.xc_cpu[ro + k] != 0 || P.xc_mem[ro + k] != 0) xr = k + 1;
+            for (uint32_t k = 0; k < ci; ++k)
+                if (P.xc_cpu[ro + cr + k] != INT64_MIN || P.xc_mem[ro + cr + k] != INT64_MIN) xi = k + 1;
+            if (cv && (P.xc_cpu[ro + cr + ci] != 0 || P.xc_mem[ro + cr + ci] != 0)) ov = 1;
+            wrong |= np > cp || xr + xi + ov > (used & 0xFFFFu);
+            for (uint32_t k = np; k < cp; ++k) wrong |= P.xp[po + k] != NONE;
+        }
+        chk = 1;
+        if (wrong) { bad = 1; first = d; }
+    }
+    audit_emit(A.rep, ESC_PAUD_CSLOT, chk, bad, first);
+}
+
+namespace {
+// podref_of with every index checked: false where the slot, its tile's class or its pairs'
+// offset lies outside the arrays (nothing is read there).
+__device__ bool paud_podref(const PodAuditDev& A, uint32_t d, PodRef& r) {
+    const PodDev& P = A.P;
+    r.flags = 0;
+    r.pair0 = r.p[0] = r.p[1] = r.p[2] = NONE;
+    const int64_t kpods = P.k_tiles * TILE;
+    if ((int64_t)d < kpods) {
+        if (P.n_cls <= 0) return false;
+        const int64_t t = d / TILE, sl = d % TILE;
+        const PodClass C = P.cls[pc_tile_class(P.cls, P.n_cls, t)];
+        if (!paud_tile_ok(A, C, t)) return false;
+        const int64_t blk = kb_block(C, t);
+        const KHead hd = kb_head(C, P.kb, blk, sl);
+        r.flags = hd.flags;
+        r.pair0 = hd.pair0;
+        for (uint32_t k = 0; k < C.nxp && k < 3; ++k) r.p[k] = kb_pair(C, P.kb, blk, k, sl);
+        return true;
+    }
+    const int64_t c = (int64_t)d - kpods, t = c / CTILE, l = c % CTILE;
+    if (c >= P.c_tiles * CTILE) return false;
+    r.flags = P.flags[c];
+    r.pair0 = P.pair0[c];
+    int64_t off = P.xp_base[t];
+    for (int64_t k = 0; k < l; ++k) off += pf_xpair(P.flags[t * CTILE + k]);
+    const uint32_t nx = pf_xpair(r.flags);
+    if (off + nx > A.n_xp) return false;
+    if (nx <= 3) {
+        for (uint32_t k = 0; k < nx; ++k) r.p[k] = P.xp[off + k];
+    } else {
+        r.flags |= POD_REF_INDIRECT;
+        r.p[0] = (uint32_t)off;
+        r.p[1] = nx;
+    }
+    return true;
+}
+}  // namespace
+
+// PODREF.  One thread per run position of the chunk: the resident PodRef against the one the
+// pod's present slot gives.
+__global__ __launch_bounds__(256) void k_paud_podref(PodAuditDev A, const PodRef* __restrict__ refs, int64_t n_refs,
+                                                     const uint32_t* __restrict__ slot, int64_t r0, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t chk = 0, bad = 0;
+    if (i < n && slot[i] != NONE) {
+        chk = 1;
+        PodRef want;
+        if (r0 + i >= n_refs || !paud_podref(A, slot[i], want)) {
+            bad = 1;
+        } else {
+            const PodRef have = refs[r0 + i];
+            bad = have.flags != want.flags || have.pair0 != want.pair0 || have.p[0] != want.p[0] || have.p[1] != want.p[1] ||
+                  have.p[2] != want.p[2];
+        }
+    }
+    audit_emit(A.rep, ESC_PAUD_PODREF, chk, bad, bad ? r0 + i : INT64_MAX);
+}
+
+// A device table against the host's copy, word by word (the class table, the tile offsets'
+// kin: small tables).
+__global__ __launch_bounds__(256) void k_paud_words(PodAuditDev A, int check, const uint32_t* __restrict__ dev,
+                                                    const uint32_t* __restrict__ host, int64_t n,
+                                                    const uint32_t* __restrict__ ids, int per, int64_t mul) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t bad = i < n && dev[i] != host[i];
+    audit_emit(A.rep, check, 0, bad, bad ? (ids ? (int64_t)ids[i / per] * mul : i) : INT64_MAX);
+}
+
+// REPLICA.  A streaming compare of two arrays, 16 B per lane and load: each thread keeps
+// PR_UNROLL loads of either array in flight (2 * PR_UNROLL wave-loads of 1 KB per wave),
+// nontemporal (nothing is read twice), the grid capped and strided over the rest.  The last
+// n_bytes % 16 bytes (whole 4-byte words) are compared by the first threads.
+constexpr int PR_UNROLL = 4;
+__global__ __launch_bounds__(256) void k_paud_replica(PodAuditDev A, const v4u32* __restrict__ x, const v4u32* __restrict__ y,
+                                                      int64_t n_bytes, int esz, int64_t code) {
+    const int64_t n16 = n_bytes / 16, stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t per16 = esz == 4 ? 4u : 2u;               // elements of one 16-B load
+    uint32_t chk = 0, bad = 0;                               // (chk: the elements this thread loaded and compared)
+    int64_t first = INT64_MAX;
+    for (int64_t base = tid; base < n16; base += stride * PR_UNROLL) {
+        v4u32 a[PR_UNROLL], b[PR_UNROLL];
+#pragma unroll
+        for (int u = 0; u < PR_UNROLL; ++u) {
+            const int64_t k = base + u * stride;
+            if (k < n16) {
+                a[u] = __builtin_nontemporal_load(x + k);
+                b[u] = __builtin_nontemporal_load(y + k);
+                chk += per16;
+            } else {
+                a[u] = b[u] = v4u32{0, 0, 0, 0};
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PR_UNROLL; ++u) {
+            const v4u32 dif = a[u] ^ b[u];
+            if (dif.x | dif.y | dif.z | dif.w) {
+                const int64_t k = base + u * stride;
+                if (esz == 4) {
+                    const uint32_t m = (dif.x ? 1u : 0u) | (dif.y ? 2u : 0u) | (dif.z ? 4u : 0u) | (dif.w ? 8u : 0u);
+                    bad += (uint32_t)__popc(m);
+                    first = imin64(first, k * 4 + (__ffs((int)m) - 1));
+                } else {
+                    const uint32_t m = ((dif.x | dif.y) ? 1u : 0u) | ((dif.z | dif.w) ? 2u : 0u);
+                    bad += (uint32_t)__popc(m);
+                    first = imin64(first, k * 2 + (__ffs((int)m) - 1));
+                }
+            }
+        }
+    }
+    const int64_t tail = (n_bytes - n16 * 16) / 4;           // < 4 words
+    if (tid < tail) {
+        const uint32_t* xw = reinterpret_cast<const uint32_t*>(x + n16);
+        const uint32_t* yw = reinterpret_cast<const uint32_t*>(y + n16);
+        if (esz == 4) {
+            ++chk;
+            if (xw[tid] != yw[tid]) { ++bad; first = imin64(first, n16 * 4 + tid); }
+        } else if (tid == 0 && tail >= 2) {                  // (one 8-byte word)
+            ++chk;
+            if (xw[0] != yw[0] || xw[1] != yw[1]) { ++bad; first = imin64(first, n16 * 2); }
+        }
+    }
+    audit_emit(A.rep, ESC_PAUD_REPLICA, chk, bad, first == INT64_MAX ? first : code | first);
+}
+
 // ===================================================================== launchers
+hipError_t launch_paud_map(const PodAuditDev& a, const int32_t* cls, const int64_t* pos, int64_t id0, int64_t n,
+                           const PodClass* hcls, int32_t n_cls, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_paud_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, cls, pos, id0, n, hcls, n_cls);
+    return hipGetLastError();
+}
+
+hipError_t launch_paud_map_cmp(const PodAuditDev& a, hipStream_t st) {
+    const int64_t w = a.n_slots / 32;
+    if (w <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_paud_map_cmp, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_paud_kslot(const PodAuditDev& a, hipStream_t st) {
+    if (a.P.k_tiles <= 0) return hipSuccess;
+    if (a.P.k_tiles > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_paud_kslot, dim3((unsigned)a.P.k_tiles), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_paud_cslot(const PodAuditDev& a, int64_t t0, int64_t nt, const uint32_t* hflags, const uint32_t* hused,
+                             const uint32_t* hxc, const uint32_t* hxp, hipStream_t st) {
+    if (nt <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_paud_cslot, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, a, t0, nt, hflags, hused, hxc, hxp);
+    return hipGetLastError();
+}
+
+hipError_t launch_paud_podref(const PodAuditDev& a, const PodRef* refs, int64_t n_refs, const uint32_t* slot, int64_t r0,
+                              int64_t n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_paud_podref, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, refs, n_refs, slot, r0, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_paud_words(const PodAuditDev& a, int check, const uint32_t* dev, const uint32_t* host, int64_t n,
+                             const uint32_t* ids, int per, int64_t mul, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_paud_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, check, dev, host, n, ids, per, mul);
+    return hipGetLastError();
+}
+
+hipError_t launch_paud_replica(const PodAuditDev& a, const void* x, const void* y, int64_t n_bytes, int esz, int64_t code,
+                               hipStream_t st) {
+    if (n_bytes < 4) return hipSuccess;
+    // memory-bound: at most 2048 workgroups (8 per CU), the rest by the grid stride
+    const int64_t need = (n_bytes / 16 + 256 * PR_UNROLL - 1) / (256 * PR_UNROLL);
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, 2048));
+    hipLaunchKernelGGL(k_paud_replica, dim3(grid), dim3(256), 0, st, a, static_cast<const v4u32*>(x),
+                       static_cast<const v4u32*>(y), n_bytes, esz, code);
+    return hipGetLastError();
+}
+
 hipError_t launch_pc_classify(const PodCompactDev& d, hipStream_t st) {
     if (d.n_cand <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_pc_classify, dim3((unsigned)((d.n_cand + 255) / 256)), dim3(256), 0, st, d);

@@ -558,6 +558,30 @@ int32_t multi_audit(esc_ctx* c, uint32_t checks, esc_audit_report* out) {
     return rc;
 }
 
+// The pod side likewise: every device audits its own shard of the pods (esc_audit_pods).
+int32_t multi_audit_pods(esc_ctx* c, uint32_t checks, esc_pod_audit_report* out) {
+    if (!out || (checks >> ESC_PAUD_N)) return ESC_E_INVAL;
+    if (M(c).diverged) return ESC_E_STATE;
+    std::memset(out, 0, sizeof *out);
+    out->ran = ~0u;
+    for (esc_audit_check& k : out->check) k.first_bad = -1;
+    const int32_t rc = seq(c, [&](int i) {
+        esc_pod_audit_report r;
+        if (int32_t e = esc_audit_pods(M(c).subs[i], checks, &r)) return e;
+        out->ran &= r.ran;
+        out->skipped |= r.skipped;
+        for (int k = 0; k < ESC_PAUD_N; ++k) {
+            out->check[k].n_checked += r.check[k].n_checked;
+            out->check[k].n_bad += r.check[k].n_bad;
+            if (r.check[k].first_bad >= 0 && (out->check[k].first_bad < 0 || r.check[k].first_bad < out->check[k].first_bad))
+                out->check[k].first_bad = r.check[k].first_bad;
+        }
+        return (int32_t)ESC_OK;
+    });
+    out->ran &= ~out->skipped;
+    return rc;
+}
+
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s) {
     if (M(c).diverged) return ESC_E_STATE;
     if (int32_t rc = nodes_relabel_check(M(c).subs[0], ids, s)) return rc;   // nothing applied anywhere

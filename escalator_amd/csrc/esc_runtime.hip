@@ -1278,6 +1278,10 @@ int32_t esc_ctx_destroy(esc_ctx* c) {
             if (c->k1t_ev[i]) hipEventDestroy(c->k1t_ev[i]);
         if (c->h_istage) hipHostFree(c->h_istage);
         c->h_istage = nullptr;
+        if (c->h_pstage) hipHostFree(c->h_pstage);
+        c->h_pstage = nullptr;
+        for (int i = 0; i < 2; ++i)
+            if (c->pstage_ev[i]) hipEventDestroy(c->pstage_ev[i]);
         if (c->h_words) hipHostFree(c->h_words);
         c->h_words = nullptr;
         if (c->h_oerr) hipHostFree(c->h_oerr);

@@ -1055,3 +1055,39 @@ func (x *Context) Audit() (*AuditReport, error) {
 	}
 	return out, nil
 }
+
+// PodAuditChecks names esc_audit_pods' checks in ESC_PAUD_* order.
+var PodAuditChecks = [C.ESC_PAUD_N]string{"MAP", "KSLOT", "CSLOT", "COUNT", "PODREF", "REPLICA"}
+
+// PodAuditReport is esc_audit_pods' report: a bit per check (1 << ESC_PAUD_*) in Ran and Skipped;
+// PODREF is skipped without a placement, REPLICA with one replica.
+type PodAuditReport struct {
+	Ran, Skipped uint32
+	Check        [C.ESC_PAUD_N]AuditCheck
+}
+
+// Clean reports whether no check that ran found a mismatch.
+func (r *PodAuditReport) Clean() bool {
+	for _, k := range r.Check {
+		if k.Bad != 0 {
+			return false
+		}
+	}
+	return true
+}
+
+// AuditPods checks the resident pod side (every check): the id map against the free lists, every
+// K position and C slot, the live counters, the PodRefs and the replicas.  Mismatches are data,
+// not an error: on !Clean() reload the snapshot, as after Audit.
+func (x *Context) AuditPods() (*PodAuditReport, error) {
+	var rep C.esc_pod_audit_report
+	if rc := C.esc_audit_pods(x.c, 0, &rep); rc != C.ESC_OK {
+		return nil, rcErr("esc_audit_pods", rc)
+	}
+	out := &PodAuditReport{Ran: uint32(rep.ran), Skipped: uint32(rep.skipped)}
+	for k := range out.Check {
+		out.Check[k] = AuditCheck{Checked: int64(rep.check[k].n_checked), Bad: int64(rep.check[k].n_bad),
+			FirstBad: int64(rep.check[k].first_bad)}
+	}
+	return out, nil
+}

@@ -876,6 +876,74 @@ typedef struct esc_audit_report {
     esc_audit_check check[ESC_AUD_N];
 } esc_audit_report;
 int32_t esc_audit(esc_ctx* ctx, uint32_t checks, esc_audit_report* out);
+/* esc_audit_pods is the pod side's counterpart: a read-only pass over the resident pod arrays
+ * and the host mirrors every pod batch is planned from.  A device slot number is t * 256 + s for
+ * K pod s of tile t and k_tiles * 256 + i for C-array index i.  A word under suspicion is never
+ * used as an index before it is compared with its array's size: out of range is a mismatch.
+ *   MAP      the host's id map (pod -> class, position) against its free lists: every pod id's
+ *            class index and position are in range and no two ids share a slot; every K
+ *            position and C slot is either mapped, or free (in a class's free list or the free
+ *            C slots; the padding slots of the C tiles, whose flags are the daemonset bit alone,
+ *            count as free), never both and never neither; the free lists name no slot twice.
+ *            first_bad: device slot; an id whose class or position is out of range is
+ *            reported as (total slots + pod id).  n_checked: the live pods by the map.
+ *   KSLOT    every K position of replica 0: a free one holds exactly a freed slot's words for
+ *            its class (what the pod pass relies on to skip it); a mapped one's stored words,
+ *            read back and classified by the rule that places pods, give the class its tile
+ *            belongs to; the device's class table equals the host's.  first_bad: device slot
+ *            (a class-table difference: the first slot of the class).  n_checked:
+ *            esc_pods_room's k_capacity.
+ *   CSLOT    every C slot of replica 0: the device flags equal the host's; a free slot carries
+ *            the daemonset bit; a live slot's pairs past the host's count are ESC_NONE and the
+ *            records the device reads as present (per kind, up to the last that is not
+ *            neutral) are no more than the host's count; the tiles' record and pair offsets
+ *            equal the host's and every tile's rooms lie inside [base[t], base[t + 1]) (the
+ *            load and esc_pods_grow lay the rooms end to end, so equality holds for every
+ *            tile; the check asks for containment, which is what keeps a read inside its
+ *            tile).  first_bad: C-array index.  n_checked: C tiles * 64.
+ *   COUNT    host only: the nine live counters esc_stream_bytes and esc_pods_slack read,
+ *            recomputed from the class table, the free lists' lengths and the C slots' counts.
+ *            first_bad: index of the first differing counter in the order live_pods,
+ *            live_c_pods, live_xc, live_xp, live_pk_pods, live_p8_pods, live_p8_xp,
+ *            live_inert_pods, live_inert_xp.  n_checked: 9.
+ *   PODREF   every bound pod's PodRef in the placement's runs against the one its present
+ *            slot gives (all of its bytes); the host's pod <-> run position maps are inverse to
+ *            each other and the runs' offsets and lengths equal the device's.  first_bad: run
+ *            position (a run-table difference: the run's first position).  n_checked: the
+ *            bound live pods.
+ *   REPLICA  every replica r >= 1 against replica 0: the K blocks, every C array, the tile
+ *            offsets, the big-tile list and the class table.  first_bad: r << 56 | array << 48
+ *            | element index, arrays numbered kb 0, flags 1, cpu0 2, pair0 3, xp 4, xc_base 5,
+ *            xp_base 6, big 7, mem0 8, xc_cpu 9, xc_mem 10, cls 11; an element is the array's
+ *            4- or 8-byte word (cls: 8-byte words).  n_checked: the elements compared.
+ * The conventions are esc_audit's: checks is a bit per check, 0 = all; PODREF without a
+ * placement and REPLICA with one replica go into `skipped` and out of `ran`; mismatches are
+ * data (ESC_OK whenever the pass ran); ESC_E_INVAL for a NULL pointer or a bit at or above
+ * ESC_PAUD_N, ESC_E_NODEV without a device, ESC_E_STATE before esc_load_pods or on a stale
+ * context.  Runs on the context's stream behind whatever is pending and writes only its own
+ * scratch: captured steps, the last decision's records, selections, reaping and new-node
+ * results, the K1 plan and its calibration stay.  Host tables go up through one pinned staging
+ * buffer kept on the context (2 x 4 MiB); one wait at the end while a table fits a half, one
+ * more per reuse of a half beyond that.  Peak extra device memory, freed on every way out: two
+ * 4 MiB chunk buffers and two bitmaps of one bit per device slot.  The array sizes the offsets
+ * are compared with are the host's, cut to the device allocations' recorded sizes: a host size
+ * past its allocation is a mismatch (KSLOT, CSLOT, PODREF at id 0; REPLICA at the first
+ * element not compared) and nothing is read past an allocation.  The report is deterministic
+ * (counts are sums, first_bad a minimum).  Multi-device: counts summed, first_bad the minimum,
+ * skipped OR-ed, ran AND-ed; the ranks of a sharded job each audit their own shard (no
+ * collective). */
+#define ESC_PAUD_MAP     0
+#define ESC_PAUD_KSLOT   1
+#define ESC_PAUD_CSLOT   2
+#define ESC_PAUD_COUNT   3
+#define ESC_PAUD_PODREF  4
+#define ESC_PAUD_REPLICA 5
+#define ESC_PAUD_N       6
+typedef struct esc_pod_audit_report {
+    uint32_t ran, skipped;           /* bit per check */
+    esc_audit_check check[ESC_PAUD_N];
+} esc_pod_audit_report;
+int32_t esc_audit_pods(esc_ctx* ctx, uint32_t checks, esc_pod_audit_report* out);
 
 /* ----------------------------------------------------------------- ordering
  * K5: per-group creation-time order of the context's node shard (a18/a19):
