@@ -100,6 +100,14 @@ class PodAuditReport(C.Structure):
     _fields_ = [("ran", u32), ("skipped", u32), ("check", AuditCheck * len(POD_AUDIT_CHECKS))]
 
 
+PV_ABSENT, PV_CLASS, PV_VALUE, PV_BIND = 1, 2, 4, 8   # ESC_PV_*: a pod's status byte from esc_pods_verify
+PODS_VERIFY_FIELDS = ["n_checked", "n_absent", "n_class", "n_value", "n_bind", "first_bad"]
+
+
+class PodsVerifyReport(C.Structure):
+    _fields_ = [(n, i64) for n in PODS_VERIFY_FIELDS]
+
+
 PODS_COMPACT_FIELDS = ["rehomed", "classes_created", "k_tiles_before", "k_tiles_after", "k1_bytes_before",
                        "k1_bytes_after", "moved", "c_free_before", "c_free_after"]
 
@@ -230,6 +238,8 @@ _SIGS = {
     "esc_new_nodes_list": (i32, [VP, i32, P(i64), P(C.c_uint8), i64, P(i64)]),
     "esc_audit": (i32, [VP, u32, P(AuditReport)]),
     "esc_audit_pods": (i32, [VP, u32, P(PodAuditReport)]),
+    "esc_pods_verify": (i32, [VP, P(i64), P(PodSoA), P(u32), P(C.c_uint8), P(PodsVerifyReport)]),
+    "esc_pods_live_ids": (i32, [VP, P(i64), i64, P(i64)]),
     "esc_set_metrics": (i32, [VP, i32]),
     "esc_metrics_results": (i32, [VP, P(GroupMetrics)]),
     "esc_use_graph": (i32, [VP, i32]),

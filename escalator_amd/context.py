@@ -710,6 +710,38 @@ class Context:
         out["skipped"] = [n for k, n in enumerate(names) if (rep.skipped >> k) & 1]
         return out
 
+    def pods_verify(self, ids, pods: dict, pod_node=None) -> tuple[np.ndarray, dict]:
+        """esc_pods_verify: a read-only compare of packed pods (a ``pack`` result, as
+        ``pods_upsert`` takes them) with what their slots hold on the device.  Returns
+        ``(status, report)``: one uint8 per pod (0 = it matches; bits ``_lib.PV_ABSENT``,
+        ``PV_CLASS``, ``PV_VALUE``, and ``PV_BIND`` when ``pod_node`` — each pod's node index,
+        ESC_NONE = unbound — is given) and the report's ``n_checked``, ``n_absent``, ``n_class``,
+        ``n_value``, ``n_bind`` and ``first_bad`` (the lowest batch index with a status, -1)."""
+        ids = np.ascontiguousarray(ids, np.int64)
+        ps, keep = pod_soa(pods)
+        status = np.zeros(len(ids), np.uint8)
+        pn = None
+        if pod_node is not None:
+            pn = np.ascontiguousarray(pod_node, np.uint32)
+            if len(pn) != len(ids):
+                raise ValueError("pod_node must have one entry per pod")
+        rep = L.PodsVerifyReport()
+        L.check(self.lib.esc_pods_verify(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ps),
+                                         pn.ctypes.data_as(C.POINTER(C.c_uint32)) if pn is not None else None,
+                                         status.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rep)), "esc_pods_verify")
+        del keep
+        return status, {n: int(getattr(rep, n)) for n in L.PODS_VERIFY_FIELDS}
+
+    def pods_live_ids(self) -> np.ndarray:
+        """esc_pods_live_ids (host only): the live pod ids, ascending."""
+        n = C.c_int64()
+        L.check(self.lib.esc_pods_live_ids(self.handle, None, 0, C.byref(n)), "esc_pods_live_ids")
+        out = np.zeros(n.value, np.int64)
+        if n.value:
+            L.check(self.lib.esc_pods_live_ids(self.handle, out.ctypes.data_as(C.POINTER(C.c_int64)), n.value, C.byref(n)),
+                    "esc_pods_live_ids")
+        return out[:n.value]
+
     # ------------------------------------------------------------- ordering
     def sort_nodes(self):
         L.check(self.lib.esc_sort_nodes(self.handle), "esc_sort_nodes")

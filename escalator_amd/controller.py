@@ -486,16 +486,23 @@ class ResidentController(Controller):
     ``pod_compact=frac`` (off by default, ``None``): after a flush that applied cleanly the pod
     side is re-laid by ``ctx.pods_compact()`` when ``ctx.pods_slack()`` reports free tiles beyond
     the load's rule plus parked pods of at least ``frac`` of the live pods
-    (``events.pod_compacts`` / ``events.pod_compact_causes``).  Pod ids and the placement stay."""
+    (``events.pod_compacts`` / ``events.pod_compact_causes``).  Pod ids and the placement stay.
+
+    ``resync_every=k`` (keyword-only, off by default, ``None``): every k-th scan's flush is
+    ``events.resync(ctx)`` — the flush, then every pod of the object store compared with the
+    device (``ctx.pods_verify``) and what differs repaired through the event calls — before the
+    audits and the decision; ``resyncs`` counts the passes, ``last_resync`` is the last result."""
 
     REBUILT_CHECKS = ("ENTRY", "FIRST", "REGION", "OCC", "TRACKER")
     # the pod audit is off unless the constructor's keyword turns it on
     pod_audit_every, pod_audits, pod_audit_failures, last_pod_audit = 0, 0, 0, None
+    # and so is the resync of the pods' values
+    resync_every, resyncs, last_resync = None, 0, None
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
                  selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0, node_rebuild: bool = False,
                  node_compact: bool = False, pod_grow: bool = False, *, pod_compact: float | None = None,
-                 pod_audit_every: int = 0):
+                 pod_audit_every: int = 0, resync_every: int | None = None):
         super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
                          selection_slack=selection_slack)
         from .events import EventQueue
@@ -519,6 +526,10 @@ class ResidentController(Controller):
         self.pod_audits = 0
         self.pod_audit_failures = 0
         self.last_pod_audit = None
+        # the pods' values: every resync_every-th scan flushes through events.resync; None = never
+        self.resync_every = int(resync_every) if resync_every else None
+        self.resyncs = 0
+        self.last_resync = None
 
     def _learned(self, name: str, j: int, t: int):
         """The queue keeps the cache: it drops a name on node_delete and re-sends the cache
@@ -564,7 +575,11 @@ class ResidentController(Controller):
             self.events.reload(self.ctx, "pod_audit:" + bad[0])
 
     def run_once(self) -> list[dict]:
-        self.events.flush(self.ctx)
+        if self.resync_every and (self.scans + 1) % self.resync_every == 0:
+            self.last_resync = self.events.resync(self.ctx)      # (flushes first)
+            self.resyncs += 1
+        else:
+            self.events.flush(self.ctx)
         self.scans += 1
         if self.audit_every and self.scans % self.audit_every == 0:
             self._audit()

@@ -6,6 +6,8 @@
 //   esc_pod_compact.hip  the pod side re-laid on the device (esc_pods_compact, esc_pods_slack,
 //                     esc_pod_where)
 //   esc_pod_audit.hip  the pod side's read-only audit (esc_audit_pods)
+//   esc_pod_verify.hip  the resident pods compared with a caller's batch (esc_pods_verify,
+//                     esc_pods_live_ids) and its kernel
 // Everything else (esc_multi.hip, esc_list.hip, the packer, the generator) sees esc_ctx as
 // opaque.  Helpers that cross a file are declared at the end, each defined in the file of its
 // subsystem; the small ones are inline here.
@@ -453,5 +455,65 @@ inline bool k_needs_pos(const esc_ctx* c, int64_t id, int ci) {
 inline bool c_keeps_slot(const esc_ctx* c, int64_t id, uint32_t f) {
     return id < (int64_t)c->pod_cls.size() && c->pod_cls[id] == -1 && c_room(c->h_cflags[c->pod_pos[id]], f);
 }
+
+// ---- the pinned staging buffer of the read-only passes (esc_audit_pods, esc_pods_verify): two
+// halves of PSTAGE_HALF bytes used in turn and a report's words behind them, kept on the context
+constexpr size_t PSTAGE_HALF = size_t(4) << 20;
+constexpr size_t PSTAGE_REP = 4096;                      // the report's words behind the halves
+inline int32_t pstage_ensure(esc_ctx* c) {
+    if (c->h_pstage) return ESC_OK;                      // (the buffer last: it marks the three as made)
+    for (hipEvent_t& e : c->pstage_ev)
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_pstage), 2 * PSTAGE_HALF + PSTAGE_REP));
+    return ESC_OK;
+}
+// The bytes from p to the end of the device allocation p lies in, as the runtime recorded it
+// (0: not a device allocation).  An allocation may be rounded up past what was asked for; it is
+// the bound that keeps a read inside mapped memory whatever the host mirrors say.
+inline int64_t dev_bytes_from(const void* p) {
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (!p || hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) return 0;
+    return (int64_t)size - (int64_t)(static_cast<const char*>(p) - static_cast<const char*>(base));
+}
+
+// Device scratch of one call, freed on every way out.
+struct PodAuditScratch {
+    std::vector<void*> bufs;
+    ~PodAuditScratch() { for (void* p : bufs) hipFree(p); }
+    template <class T>
+    hipError_t get(T** p, size_t n) {
+        const hipError_t e = dalloc(p, n);
+        if (e == hipSuccess) bufs.push_back(*p);
+        return e;
+    }
+};
+
+// The staging halves in turn.  next(): the half to fill (after its last use is over);
+// send(dst, bytes): the half's first bytes to device memory dst (null: the half's own chunk
+// buffer); done(): everything enqueued so far is the half's last use.
+struct Stager {
+    esc_ctx* c;
+    hipStream_t st;
+    uint8_t* dev[2] = {nullptr, nullptr};
+    bool used[2] = {false, false};
+    int h = 1;
+    uint8_t* host() const { return c->h_pstage + (size_t)h * PSTAGE_HALF; }
+    uint8_t* chunk() const { return dev[h]; }
+    int32_t next() {
+        h ^= 1;
+        if (used[h]) HIP_TRY(hipEventSynchronize(c->pstage_ev[h]));
+        return ESC_OK;
+    }
+    int32_t send(void* dst, size_t at, size_t bytes) {
+        if (bytes) HIP_TRY(hipMemcpyAsync(dst ? dst : dev[h] + at, host() + at, bytes, hipMemcpyHostToDevice, st));
+        return ESC_OK;
+    }
+    int32_t done() {
+        HIP_TRY(hipEventRecord(c->pstage_ev[h], st));
+        used[h] = true;
+        return ESC_OK;
+    }
+};
 
 }  // namespace esc

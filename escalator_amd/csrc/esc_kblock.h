@@ -391,4 +391,73 @@ ESC_KB_HD int kb_pod_class(const PodClass& C, const uint32_t* kb, int64_t blk, i
     return pod_class_id(h.flags, (uint32_t)h.cpu0, h.mem0, h.pair0, r.xc, r.xm, r.xp, n_gp);
 }
 
+// Every word a pod occupies in a C slot (esc_pods_upsert into a C slot): put(array, index,
+// value) with array one of CArr.  cf: the slot's flags, whose counts are its room; d: its
+// C-array index; ro / po: its first record / pair in the record and pair arrays.  The slot keeps
+// its counts and takes the pod's own bits; the pod's records and pairs come first of each kind in
+// the room and the rest is neutral (0 for regular and overhead records, INT64_MIN for init keys,
+// NONE for pairs).  The room must hold the pod (c_room, esc_pod_layout.h).
+enum CArr : int { CA_FLAGS = 0, CA_CPU0, CA_MEM0, CA_PAIR0, CA_XC_CPU, CA_XC_MEM, CA_XP };
+template <class Put>
+ESC_KB_HD void c_write_pod(uint32_t cf, int64_t d, int64_t ro, int64_t po, uint32_t f, uint32_t cpu0, int64_t mem0,
+                           uint32_t pair0, const int64_t* xc_cpu, const int64_t* xc_mem, const uint32_t* xp, Put&& put) {
+    put(CA_FLAGS, d, (uint64_t)((cf & ~KP_POD_FLAGS) | (f & KP_POD_FLAGS)));
+    put(CA_CPU0, d, (uint64_t)cpu0);
+    put(CA_MEM0, d, (uint64_t)mem0);
+    put(CA_PAIR0, d, (uint64_t)pair0);
+    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u;
+    int64_t o = ro;
+    for (uint32_t k = 0; k < pf_xreg(cf); ++k, ++o) {
+        put(CA_XC_CPU, o, (uint64_t)(k < xr ? xc_cpu[k] : 0));
+        put(CA_XC_MEM, o, (uint64_t)(k < xr ? xc_mem[k] : 0));
+    }
+    for (uint32_t k = 0; k < pf_xinit(cf); ++k, ++o) {
+        put(CA_XC_CPU, o, (uint64_t)(k < xi ? xc_cpu[xr + k] : INT64_MIN));
+        put(CA_XC_MEM, o, (uint64_t)(k < xi ? xc_mem[xr + k] : INT64_MIN));
+    }
+    if (cf & ESC_PF_HAS_OVH) {
+        put(CA_XC_CPU, o, (uint64_t)(ov ? xc_cpu[xr + xi] : 0));
+        put(CA_XC_MEM, o, (uint64_t)(ov ? xc_mem[xr + xi] : 0));
+    }
+    const uint32_t nx = pf_xpair(f);
+    for (uint32_t k = 0; k < pf_xpair(cf); ++k) put(CA_XP, po + k, (uint64_t)(k < nx ? xp[k] : NONE));
+}
+
+// esc_pods_verify.  Does K slot sl of the block at word blk of class C hold exactly
+// what kb_write_pod would write for this pod?  The writer's own walk with a put that reads and
+// compares: get(width, index) returns the stored word, widths and indices as put's.  The
+// differences are or-ed, not tested one by one, so that a lane's loads are all in flight before
+// the first is needed.  The class must be the pod's (pod_class_id == kb_class_id(C)): its rows
+// are then as many as the pod's records and pairs.
+template <class Get>
+ESC_KB_HD bool kb_pod_same(const PodClass& C, int64_t blk, int64_t sl, uint32_t f, uint32_t cpu0, int64_t mem0,
+                           uint32_t pair0, const int64_t* xc_cpu, const int64_t* xc_mem, const uint32_t* xp, Get&& get) {
+    uint64_t diff = 0;
+    kb_write_pod(C, blk, sl, f, cpu0, mem0, pair0, xc_cpu, xc_mem, xp, [&](int width, int64_t at, uint64_t v) {
+        const uint64_t m = width == 8 ? ~uint64_t(0) : (width == 4 ? uint64_t(0xFFFFFFFFu) : uint64_t(0xFFFFu));
+        diff |= ((uint64_t)get(width, at) ^ v) & m;
+    });
+    return diff == 0;
+}
+// The same over K blocks in memory.
+ESC_KB_HD bool kb_pod_same(const PodClass& C, const uint32_t* kb, int64_t blk, int64_t sl, uint32_t f, uint32_t cpu0,
+                           int64_t mem0, uint32_t pair0, const int64_t* xc_cpu, const int64_t* xc_mem,
+                           const uint32_t* xp) {
+    return kb_pod_same(C, blk, sl, f, cpu0, mem0, pair0, xc_cpu, xc_mem, xp, [&](int width, int64_t at) -> uint64_t {
+        if (width == 8) return (uint64_t)reinterpret_cast<const int64_t*>(kb)[at];
+        if (width == 4) return (uint64_t)kb[at];
+        return (uint64_t)reinterpret_cast<const uint16_t*>(kb)[at];
+    });
+}
+// Does C slot d (flags cf, records from ro, pairs from po) hold exactly what c_write_pod would
+// write for this pod?  get(array, index) returns the stored word of a CArr array.
+template <class Get>
+ESC_KB_HD bool c_pod_same(uint32_t cf, int64_t d, int64_t ro, int64_t po, uint32_t f, uint32_t cpu0, int64_t mem0,
+                          uint32_t pair0, const int64_t* xc_cpu, const int64_t* xc_mem, const uint32_t* xp, Get&& get) {
+    uint64_t diff = 0;
+    c_write_pod(cf, d, ro, po, f, cpu0, mem0, pair0, xc_cpu, xc_mem, xp,
+                [&](int arr, int64_t at, uint64_t v) { diff |= (uint64_t)get(arr, at) ^ v; });
+    return diff == 0;
+}
+
 }  // namespace esc

@@ -75,6 +75,9 @@ int32_t multi_new_nodes_eval(esc_ctx* c, const int64_t* since_ns, esc_new_nodes*
 int32_t multi_new_nodes_list(esc_ctx* c, int32_t g, int64_t* idx, uint8_t* known, int64_t cap, int64_t* n_out);
 int32_t multi_audit(esc_ctx* c, uint32_t checks, esc_audit_report* out);              // every device, merged
 int32_t multi_audit_pods(esc_ctx* c, uint32_t checks, esc_pod_audit_report* out);    // likewise
+int32_t multi_pods_verify(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, const uint32_t* pod_node, uint8_t* status_out,
+                          esc_pods_verify_report* out);                           // routed by id, merged in batch order
+int32_t multi_pods_live_ids(const esc_ctx* c, int64_t* ids_out, int64_t cap, int64_t* n_out);
 int32_t multi_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out);
 int32_t multi_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_nodes_rebuild(esc_ctx* c);                                          // every device's node side (esc_nodes_rebuild)

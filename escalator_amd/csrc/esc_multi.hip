@@ -350,11 +350,14 @@ int32_t multi_k1_calibrate(esc_ctx* c, int32_t rounds) {
 
 // ---------------------------------------------------------------- informer events
 // A pod event batch split by the devices' shards (owner_of_pod), ids made shard-local.
-static int32_t split_pod_batch(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, std::vector<PodBatch>& b) {
+// idx (optional): every device's pods' indices in the batch.
+static int32_t split_pod_batch(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, std::vector<PodBatch>& b,
+                               std::vector<std::vector<int64_t>>* idx = nullptr) {
     if (!p || p->n_pods < 0 || (p->n_pods > 0 && (!ids || !p->flags || !p->cpu0 || !p->mem0 || !p->pair0)))
         return ESC_E_INVAL;
     if (M(c).pod_lo.empty()) return ESC_E_STATE;
     b.assign((size_t)nsub(c), PodBatch());
+    if (idx) idx->assign((size_t)nsub(c), std::vector<int64_t>());
     int64_t oc = 0, op = 0;
     for (int64_t i = 0; i < p->n_pods; ++i) {
         const uint32_t f = p->flags[i], nc = pf_xctr(f), nx = pf_xpair(f);
@@ -363,6 +366,7 @@ static int32_t split_pod_batch(esc_ctx* c, const int64_t* ids, const esc_pod_soa
         const int s = owner_of_pod(c, ids[i]);
         PodBatch& x = b[s];
         x.ids.push_back(ids[i] - M(c).pod_lo[s]);
+        if (idx) (*idx)[s].push_back(i);
         x.flags.push_back(f);
         x.cpu0.push_back(p->cpu0[i]);
         x.mem0.push_back(p->mem0[i]);
@@ -580,6 +584,60 @@ int32_t multi_audit_pods(esc_ctx* c, uint32_t checks, esc_pod_audit_report* out)
     });
     out->ran &= ~out->skipped;
     return rc;
+}
+
+// esc_pods_verify: the batch routed by id to the shard that holds it (as multi_pods_upsert routes
+// it), every device verifying its share; the statuses go back to their batch positions, the
+// counts are summed and first_bad is the lowest batch index.  A batch invalid as a whole (an id
+// named twice lands on one device) is refused by the device that sees it, before any report.
+int32_t multi_pods_verify(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, const uint32_t* pod_node, uint8_t* status_out,
+                          esc_pods_verify_report* out) {
+    if (!out) return ESC_E_INVAL;
+    if (M(c).diverged) return ESC_E_STATE;
+    const int k = nsub(c);
+    std::vector<PodBatch> b;
+    std::vector<std::vector<int64_t>> idx;
+    if (int32_t rc = split_pod_batch(c, ids, p, b, &idx)) return rc;
+    esc_pods_verify_report sum = {0, 0, 0, 0, 0, -1};
+    std::vector<uint8_t> all((size_t)std::max<int64_t>(p->n_pods, 1), 0);
+    for (int s = 0; s < k; ++s) {
+        const esc_pod_soa v = b[s].view();
+        const int64_t m = v.n_pods;
+        std::vector<uint32_t> nodes;
+        if (pod_node)
+            for (int64_t j : idx[s]) nodes.push_back(pod_node[j]);
+        std::vector<uint8_t> stat((size_t)std::max<int64_t>(m, 1), 0);
+        esc_pods_verify_report r;
+        if (int32_t rc = esc_pods_verify(M(c).subs[s], b[s].ids.data(), &v, pod_node ? nodes.data() : nullptr, stat.data(), &r)) return rc;
+        for (int64_t j = 0; j < m; ++j) all[(size_t)idx[s][j]] = stat[j];
+        sum.n_checked += r.n_checked; sum.n_absent += r.n_absent; sum.n_class += r.n_class;
+        sum.n_value += r.n_value; sum.n_bind += r.n_bind;
+    }
+    for (int64_t i = 0; i < p->n_pods && sum.first_bad < 0; ++i)
+        if (all[(size_t)i]) sum.first_bad = i;
+    if (status_out && p->n_pods) std::memcpy(status_out, all.data(), (size_t)p->n_pods);
+    *out = sum;
+    return ESC_OK;
+}
+
+// esc_pods_live_ids: the union over the shards, every shard's ids made global (ascending: the
+// shards' id ranges ascend).
+int32_t multi_pods_live_ids(const esc_ctx* c, int64_t* ids_out, int64_t cap, int64_t* n_out) {
+    if (!n_out || cap < 0 || (cap > 0 && !ids_out)) return ESC_E_INVAL;
+    if (M(c).pod_lo.empty()) return ESC_E_STATE;
+    int64_t total = 0;
+    for (int s = 0; s < nsub(c); ++s) {
+        int64_t m = 0;
+        const int32_t rc = esc_pods_live_ids(M(c).subs[s], nullptr, 0, &m);
+        if (rc) return rc;
+        if (total + m <= cap && m) {
+            if (int32_t e = esc_pods_live_ids(M(c).subs[s], ids_out + total, m, &m)) return e;
+            for (int64_t j = 0; j < m; ++j) ids_out[total + j] += M(c).pod_lo[s];
+        }
+        total += m;
+    }
+    *n_out = total;
+    return total > cap && !(cap == 0 && !ids_out) ? ESC_E_LIMIT : ESC_OK;
 }
 
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s) {

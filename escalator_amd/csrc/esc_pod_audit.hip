@@ -15,8 +15,6 @@ using namespace esc;
 
 namespace {
 
-constexpr size_t PSTAGE_HALF = size_t(4) << 20;
-constexpr size_t PSTAGE_REP = 4096;                      // the report's words behind the halves
 #if ESC_MEASURE
 // This thread's last REPLICA pass (measurement library: scripts/pod_audit_probe.py turns them
 // into a bandwidth): the bytes of one replica it compared (each is read from two replicas) and
@@ -24,54 +22,6 @@ constexpr size_t PSTAGE_REP = 4096;                      // the report's words b
 thread_local int64_t g_paud_replica_bytes = 0;
 thread_local float g_paud_replica_ms = 0;
 #endif
-// The bytes from p to the end of the device allocation p lies in, as the runtime recorded it
-// (0: not a device allocation).  An allocation may be rounded up past what was asked for; it is
-// the bound that keeps a read inside mapped memory whatever the host mirrors say.
-int64_t dev_bytes_from(const void* p) {
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (!p || hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) return 0;
-    return (int64_t)size - (int64_t)(static_cast<const char*>(p) - static_cast<const char*>(base));
-}
-
-struct PodAuditScratch {
-    std::vector<void*> bufs;
-    ~PodAuditScratch() { for (void* p : bufs) hipFree(p); }
-    template <class T>
-    hipError_t get(T** p, size_t n) {
-        const hipError_t e = dalloc(p, n);
-        if (e == hipSuccess) bufs.push_back(*p);
-        return e;
-    }
-};
-
-// The staging halves in turn.  next(): the half to fill (after its last use is over);
-// send(dst, bytes): the half's first bytes to device memory dst (null: the half's own chunk
-// buffer); done(): everything enqueued so far is the half's last use.
-struct Stager {
-    esc_ctx* c;
-    hipStream_t st;
-    uint8_t* dev[2] = {nullptr, nullptr};
-    bool used[2] = {false, false};
-    int h = 1;
-    uint8_t* host() const { return c->h_pstage + (size_t)h * PSTAGE_HALF; }
-    uint8_t* chunk() const { return dev[h]; }
-    int32_t next() {
-        h ^= 1;
-        if (used[h]) HIP_TRY(hipEventSynchronize(c->pstage_ev[h]));
-        return ESC_OK;
-    }
-    int32_t send(void* dst, size_t at, size_t bytes) {
-        if (bytes) HIP_TRY(hipMemcpyAsync(dst ? dst : dev[h] + at, host() + at, bytes, hipMemcpyHostToDevice, st));
-        return ESC_OK;
-    }
-    int32_t done() {
-        HIP_TRY(hipEventRecord(c->pstage_ev[h], st));
-        used[h] = true;
-        return ESC_OK;
-    }
-};
-
 void paud_bad(esc_audit_check& k, int64_t id) {
     ++k.n_bad;
     if (k.first_bad < 0 || id < k.first_bad) k.first_bad = id;
@@ -131,11 +81,7 @@ int32_t audit_pods_one(esc_ctx* c, uint32_t checks, esc_pod_audit_report* out) {
 
     hipSetDevice(c->device);
     hipStream_t st = c->stream;
-    if (!c->h_pstage) {                                      // (the buffer last: it marks the three as made)
-        for (hipEvent_t& e : c->pstage_ev)
-            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_pstage), 2 * PSTAGE_HALF + PSTAGE_REP));
-    }
+    if (int32_t rc = pstage_ensure(c)) return rc;
     const int64_t n_cls = (int64_t)c->h_cls.size(), kt = c->k_tiles, ct = c->c_tiles, npad = ct * CTILE;
     const int64_t kslots = kt * TILE, n_slots = kslots + npad;
     // The sizes every offset is compared with are the host's, cut to the device allocations' own

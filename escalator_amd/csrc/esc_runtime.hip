@@ -3081,21 +3081,12 @@ bool upsert_c(esc_ctx* c, int64_t id, int64_t d, const esc_pod_soa* p, int64_t i
     const int64_t t = d / CTILE;
     uint32_t ro = c->h_xc_base[t], po = c->h_xp_base[t];
     for (int64_t k = t * CTILE; k < d; ++k) { ro += pf_xctr(c->h_cflags[k]); po += pf_xpair(c->h_cflags[k]); }
-    P.add(PT_FLAGS, d, nf);
-    P.add(PT_CPU0, d, p->cpu0[i]);
-    P.add(PT_MEM0, d, (uint64_t)p->mem0[i]);
-    P.add(PT_PAIR0, d, p->pair0[i]);
-    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u;
-    auto rec = [&](uint32_t at, bool have, int64_t src, int64_t neutral) {
-        P.add(PT_XC_CPU, at, (uint64_t)(have ? p->xc_cpu[src] : neutral));
-        P.add(PT_XC_MEM, at, (uint64_t)(have ? p->xc_mem[src] : neutral));
-    };
-    uint32_t o = ro;
-    for (uint32_t k = 0; k < pf_xreg(cf); ++k) rec(o++, k < xr, rof + k, 0);
-    for (uint32_t k = 0; k < pf_xinit(cf); ++k) rec(o++, k < xi, rof + xr + k, INT64_MIN);
-    if (cf & ESC_PF_HAS_OVH) rec(o++, ov != 0, rof + xr + xi, 0);
-    const uint32_t nx = pf_xpair(f);
-    for (uint32_t k = 0; k < pf_xpair(cf); ++k) P.add(PT_XP, po + k, k < nx ? p->xp_pair[pof + k] : NONE);
+    // (the words are c_write_pod's, esc_kblock.h: esc_pods_verify compares by the same walk)
+    static constexpr uint32_t pt_of[7] = {PT_FLAGS, PT_CPU0, PT_MEM0, PT_PAIR0, PT_XC_CPU, PT_XC_MEM, PT_XP};
+    const uint32_t xr = pf_xreg(f), xi = pf_xinit(f), ov = (f & ESC_PF_HAS_OVH) ? 1u : 0u, nx = pf_xpair(f);
+    c_write_pod(cf, d, ro, po, f, p->cpu0[i], p->mem0[i], p->pair0[i], xr + xi + ov ? p->xc_cpu + rof : nullptr,
+                xr + xi + ov ? p->xc_mem + rof : nullptr, nx ? p->xp_pair + pof : nullptr,
+                [&](int arr, int64_t at, uint64_t v) { P.add(pt_of[arr], at, v); });
     c->h_cflags[d] = nf;
     c->h_cused[d] = (xr + xi + ov) | nx << 16;
     ++c->live_pods;

@@ -17,6 +17,8 @@ pod reloaded, every id kept) and one retry; a second limit reloads.  With ``pod_
 flush that applied cleanly is followed by one ``pods_compact`` (the pod side re-laid on the device:
 classes shrunk to the load's rule, parked pods back in their classes, every id kept) when
 ``pods_slack`` reports ``(k_tiles - k_tiles_rule) * 256 + parked >= frac * live pods``.
+``resync(ctx)`` is the informers' periodic resync: the whole object store compared with the device
+(``pods_verify``) and only what differs repaired through the calls above.
 
 It holds the current objects (plain-dict records, escalator_amd/objects.py) — the truth a
 reload is built from — and, beside them, what the device last saw of each.  Ingest
@@ -94,6 +96,8 @@ class EventQueue:
         self.pod_compacts = 0
         self.pod_compact_causes: list[str] = []    # "slack" (free tiles alone reach the threshold) / "parked"
         self.pod_compact_failures = 0
+        self.resyncs = 0                           # resync() calls, and the pods each kind of repair took
+        self.resync_repairs = {"absent": 0, "class": 0, "value": 0, "bind": 0, "orphans": 0}
         self.pods: dict[str, dict] = {}            # the object store: key -> pod, name -> node
         self.nodes: dict[str, dict] = {}           # (insertion order = arrival order)
         self._dev_pods: dict[str, dict] = {}       # the records the device holds, as last flushed
@@ -358,19 +362,7 @@ class EventQueue:
         upsert = born + [k for k in changed if _pod_spec(dev_p[k]) != _pod_spec(self.pods[k])]
         for k in born:
             pid[k] = self._take_id()
-        if upsert:
-            packed, _ = ctx.pack([self.pods[k] for k in upsert], [])
-            ids = np.array([pid[k] for k in upsert], np.int64)
-            try:
-                self._call("pods_upsert", len(upsert), ctx.pods_upsert, ids, packed)
-            except _Reload:
-                if not self.pod_grow:
-                    raise
-                # a full class or C section: grown on the device for this batch, then one retry
-                self._call("pods_upsert", 0, ctx.pods_grow, ids, packed)
-                self.pod_grows += 1
-                self.pod_grow_causes.append("pods_upsert")
-                self._call("pods_upsert", len(upsert), ctx.pods_upsert, ids, packed)
+        self._upsert_pods(ctx, upsert)
         bind = list(born)
         seen = set(born)
         for k in changed:
@@ -385,18 +377,103 @@ class EventQueue:
         for k in dirty_p:
             if k in self.pods:
                 dev_p[k] = self.pods[k]
-        if bind:
-            ids = np.array([pid[k] for k in bind], np.int64)
-            try:
-                self._call("pods_bind", len(bind), ctx.pods_bind, ids,
-                           np.array([self._target(self.pods[k]) for k in bind], np.uint32))
-            except _Reload:
-                if not self.compact:
-                    raise
-                # a full run: the compaction re-cuts the runs (the targets' indices change with it)
-                self.node_compact(ctx, "pods_bind")
-                self._call("pods_bind", len(bind), ctx.pods_bind, ids,
-                           np.array([self._target(self.pods[k]) for k in bind], np.uint32))
+        self._bind_pods(ctx, bind)
+
+    def _upsert_pods(self, ctx, keys):
+        """One ``pods_upsert`` of the store's pods `keys` under their ids; with ``pod_grow`` on
+        its first ESC_E_LIMIT is answered by one ``pods_grow`` and one retry."""
+        if not keys:
+            return
+        pid = self._pod_id
+        packed, _ = ctx.pack([self.pods[k] for k in keys], [])
+        ids = np.array([pid[k] for k in keys], np.int64)
+        try:
+            self._call("pods_upsert", len(keys), ctx.pods_upsert, ids, packed)
+        except _Reload:
+            if not self.pod_grow:
+                raise
+            # a full class or C section: grown on the device for this batch, then one retry
+            self._call("pods_upsert", 0, ctx.pods_grow, ids, packed)
+            self.pod_grows += 1
+            self.pod_grow_causes.append("pods_upsert")
+            self._call("pods_upsert", len(keys), ctx.pods_upsert, ids, packed)
+
+    def _bind_pods(self, ctx, keys):
+        """One ``pods_bind`` of the store's pods `keys` to their nodes; with ``compact`` on a full
+        run is answered by one ``nodes_compact`` and one retry."""
+        if not keys:
+            return
+        ids = np.array([self._pod_id[k] for k in keys], np.int64)
+        try:
+            self._call("pods_bind", len(keys), ctx.pods_bind, ids,
+                       np.array([self._target(self.pods[k]) for k in keys], np.uint32))
+        except _Reload:
+            if not self.compact:
+                raise
+            # a full run: the compaction re-cuts the runs (the targets' indices change with it)
+            self.node_compact(ctx, "pods_bind")
+            self._call("pods_bind", len(keys), ctx.pods_bind, ids,
+                       np.array([self._target(self.pods[k]) for k in keys], np.uint32))
+
+    # ------------------------------------------------------------------ resync
+    def resync(self, ctx, chunk: int = 65536) -> dict:
+        """The informers' resync (pkg/k8s/cache.go:27,48) for the resident snapshot: after a
+        flush, every pod of the object store is packed as a flush packs it and compared with what
+        its slot holds on the device (``pods_verify``, `chunk` pods per call), bindings included,
+        and the device's live ids are compared with the identity map.  What differs is repaired
+        through the flush's own paths, an ESC_E_LIMIT answered as a flush answers it
+        (``pods_grow`` / ``nodes_compact`` when enabled, else one reload): the pods reported
+        absent, of another class or with another value in one ``pods_upsert``, the pods bound
+        elsewhere in one ``pods_bind``, the ids no pod of the store has in one ``pods_delete``.
+        Returns ``{checked, absent, class, value, bind, orphans, reloaded}``."""
+        from ._lib import PV_ABSENT, PV_BIND, PV_CLASS, PV_VALUE
+        self.flush(ctx)
+        self.resyncs += 1
+        pid = self._pod_id
+        out = {"checked": 0, "absent": 0, "class": 0, "value": 0, "bind": 0, "orphans": 0, "reloaded": False}
+        keys = [k for k in self.pods if k in pid]
+        upsert, bind = [], []
+        for a in range(0, len(keys), max(1, int(chunk))):
+            ks = keys[a:a + max(1, int(chunk))]
+            packed, _ = ctx.pack([self.pods[k] for k in ks], [])
+            status, _rep = ctx.pods_verify(np.array([pid[k] for k in ks], np.int64), packed,
+                                           np.array([self._target(self.pods[k]) for k in ks], np.uint32))
+            status = np.asarray(status, np.uint8)
+            out["checked"] += len(ks)
+            for name, bit in (("absent", PV_ABSENT), ("class", PV_CLASS), ("value", PV_VALUE), ("bind", PV_BIND)):
+                out[name] += int(np.count_nonzero(status & bit))
+            upsert += [ks[i] for i in np.flatnonzero(status & (PV_ABSENT | PV_CLASS | PV_VALUE))]
+            bind += [ks[i] for i in np.flatnonzero(status & PV_BIND)]
+        # the other direction: ids the device holds for no pod of the store (an id the map still
+        # names for a key the store lost is one of them: its delete never arrived)
+        known = {pid[k] for k in keys}
+        orphans = [int(i) for i in ctx.pods_live_ids() if int(i) not in known]
+        out["orphans"] = len(orphans)
+        log = logging.getLogger(__name__)
+        for name in ("absent", "class", "value", "bind", "orphans"):
+            if out[name]:
+                self.resync_repairs[name] += out[name]
+                log.warning("resync: %d pods %s", out[name],
+                            {"absent": "missing on the device", "class": "in another class on the device",
+                             "value": "with other values on the device", "bind": "bound elsewhere on the device",
+                             "orphans": "on the device and not in the store"}[name])
+        try:
+            self._upsert_pods(ctx, upsert)
+            self._bind_pods(ctx, bind)
+            if orphans:
+                self._call("pods_delete", len(orphans), ctx.pods_delete, np.array(orphans, np.int64))
+        except _Reload as e:
+            self.reload_causes.append("resync:%s" % e)
+            self._reload(ctx, {}, {})
+            out["reloaded"] = True
+            return out
+        for k in upsert + bind:
+            self._dev_pods[k] = self.pods[k]
+        gone = set(orphans)
+        for k in [k for k, i in pid.items() if i in gone and k not in self.pods]:
+            heapq.heappush(self._free, pid.pop(k))
+            self._dev_pods.pop(k, None)
+        return out
 
     def _reload(self, ctx, dirty_p, dirty_n):
         """One full load from the object store: the nodes the device held keep their order

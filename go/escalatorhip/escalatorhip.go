@@ -1091,3 +1091,68 @@ func (x *Context) AuditPods() (*PodAuditReport, error) {
 	}
 	return out, nil
 }
+
+// A pod's status byte from PodsVerify (ESC_PV_*): 0 = the device holds the pod as offered.
+const (
+	PodAbsent uint8 = C.ESC_PV_ABSENT // the id is not a live pod of the context
+	PodClass  uint8 = C.ESC_PV_CLASS  // the pod's class (or a C slot's room) is not the one it lies in
+	PodValue  uint8 = C.ESC_PV_VALUE  // a stored word differs
+	PodBind   uint8 = C.ESC_PV_BIND   // the placement binds the pod elsewhere (or-ed)
+)
+
+// PodsVerifyReport is esc_pods_verify's report; FirstBad is the lowest batch index with a
+// non-zero status, -1 if none.
+type PodsVerifyReport struct {
+	Checked, Absent, Class, Value, Bind, FirstBad int64
+}
+
+// PodsVerify compares pods, as the informer's store holds them, with what their slots hold on
+// the device (the value half of the informers' resync): read-only, one status byte per pod.
+// nodeIdx (nil: bindings not compared) is every pod's node index, None = unbound.  Mismatches are
+// data, not an error: send PodAbsent / PodClass / PodValue pods through PodsUpsert and PodBind
+// pods through PodsBind.
+func (x *Context) PodsVerify(ids []int64, pods []*v1.Pod, nodeIdx []uint32) ([]uint8, *PodsVerifyReport, error) {
+	if len(ids) != len(pods) || (nodeIdx != nil && len(nodeIdx) != len(ids)) {
+		return nil, nil, fmt.Errorf("escalatorhip: %d ids, %d pods, %d node indices", len(ids), len(pods), len(nodeIdx))
+	}
+	status := make([]uint8, len(ids))
+	out := &PodsVerifyReport{FirstBad: -1}
+	if len(ids) == 0 {
+		return status, out, nil
+	}
+	err := x.pack(pods, nil, nil, false, func(ps *C.esc_pod_soa, _ *C.esc_node_soa) error {
+		var rep C.esc_pods_verify_report
+		var pn *C.uint32_t
+		if nodeIdx != nil {
+			pn = (*C.uint32_t)(unsafe.Pointer(ptr(nodeIdx)))
+		}
+		rc := C.esc_pods_verify(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), ps, pn, (*C.uint8_t)(unsafe.Pointer(ptr(status))), &rep)
+		if rc != C.ESC_OK {
+			return rcErr("esc_pods_verify", rc)
+		}
+		*out = PodsVerifyReport{Checked: int64(rep.n_checked), Absent: int64(rep.n_absent), Class: int64(rep.n_class),
+			Value: int64(rep.n_value), Bind: int64(rep.n_bind), FirstBad: int64(rep.first_bad)}
+		return nil
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	return status, out, nil
+}
+
+// PodsLiveIDs returns the live pod ids of the context, ascending (host only): the other direction
+// of a resync, the pods the device holds and the store does not (PodsDelete them).
+func (x *Context) PodsLiveIDs() ([]int64, error) {
+	var n C.int64_t
+	if rc := C.esc_pods_live_ids(x.c, nil, 0, &n); rc != C.ESC_OK {
+		return nil, rcErr("esc_pods_live_ids", rc)
+	}
+	ids := make([]int64, int(n))
+	if n == 0 {
+		return ids, nil
+	}
+	if rc := C.esc_pods_live_ids(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), n, &n); rc != C.ESC_OK {
+		return nil, rcErr("esc_pods_live_ids", rc)
+	}
+	return ids[:int(n)], nil
+}

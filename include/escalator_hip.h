@@ -944,6 +944,63 @@ typedef struct esc_pod_audit_report {
     esc_audit_check check[ESC_PAUD_N];
 } esc_pod_audit_report;
 int32_t esc_audit_pods(esc_ctx* ctx, uint32_t checks, esc_pod_audit_report* out);
+/* esc_pods_verify is the value half of the informers' resync: a read-only compare of a batch of
+ * pods, as the caller's store holds them, with the bytes their slots hold on the device.  ids and
+ * pods are exactly what esc_pods_upsert takes.  Pod i of the batch gets one status byte:
+ *   0              the pod matches: its id is live, it lies where a pod of its class lies and
+ *                  every word esc_pods_upsert would write for it equals the stored word
+ *   ESC_PV_ABSENT  the id is not a live pod of the context
+ *   ESC_PV_CLASS   a K-resident pod whose class (the rule that places pods) is not the class it
+ *                  lies in; a C-resident pod its slot's room does not hold; a pod whose place by
+ *                  the host mirrors lies outside the device arrays (nothing is read there)
+ *   ESC_PV_VALUE   a stored word differs.  CLASS and VALUE exclude each other: a class mismatch
+ *                  ends the compare of that pod
+ *   ESC_PV_BIND    or-ed in when pod_node is given: the placement's binding of the pod differs
+ *                  from pod_node[i], both normalised alike (ESC_NONE, an index outside the node
+ *                  table and an absent slot all mean unbound; an absent pod is bound nowhere, so
+ *                  ABSENT | BIND says that the store's pod is bound)
+ * The stored form decides, so the lossy encodings compare as stored: a packed small pod's static,
+ * has-selector and affinity bits are one bit, its pairs that no group selects are all "none",
+ * and a packed pod's container records are their fold (the same effective request matches,
+ * whatever the split); a plain class and a C slot keep every record.  A K-holdable pod parked in
+ * a C slot matches when its words do.  Replica 0 is the one compared (esc_audit_pods' REPLICA
+ * covers the others) and the device PodRefs are not (esc_audit_pods' PODREF compares them with
+ * the slots; BIND compares the host's binding mirror they are written from).
+ * The report: n_checked = n_pods, a count per status bit and first_bad, the lowest batch index
+ * with a non-zero status (-1: none); status_out ([n_pods]) may be NULL.  Deterministic: counts are
+ * sums, first_bad a minimum.  Mismatches are data (ESC_OK); nothing is repaired: the caller sends
+ * ABSENT / CLASS / VALUE pods through esc_pods_upsert and BIND pods through esc_pods_bind.
+ * ESC_E_INVAL with nothing reported for a batch esc_pods_upsert would call invalid (repeated
+ * ids, ids outside [0, 2^31), unsorted pair lists, counts past the arrays) and for a NULL out;
+ * ESC_E_NODEV without a device; ESC_E_STATE before esc_load_pods, on a stale context, or with
+ * pod_node given and no placement loaded; n_pods == 0 is ESC_OK with a zero report.
+ * Read-only, as esc_audit_pods is: it runs on the context's stream behind whatever is pending and
+ * writes only its own scratch; captured steps, the last decision's records, selections, reaping
+ * and new-node results, the K1 plan and its calibration stay.  Every pod's place (its class and
+ * position, or its C slot and that slot's record and pair offsets) comes from the host mirrors
+ * alone and is compared with the device allocations' recorded sizes before the launch: no
+ * device-resident word is used as an index.  The batch goes up in chunks through esc_audit_pods'
+ * pinned staging buffer, so the extra device memory (two 4 MiB chunk buffers and the host's class
+ * table) does not grow with n_pods.  Multi-device: the batch is routed by id to the shard that
+ * holds it, as esc_pods_upsert routes it; statuses return in batch order, counts are summed and
+ * first_bad is the minimum batch index; the ranks of a sharded job each verify their own shard
+ * (no collective).
+ * esc_pods_live_ids (host only): the live pod ids, ascending, for the other direction of a
+ * resync (pods the context holds and the store does not).  ids_out == NULL with cap == 0 sizes
+ * the answer (*n_out); ESC_E_LIMIT when cap is short (*n_out still set); ESC_E_STATE before
+ * esc_load_pods.  Multi-device: the union over the shards. */
+#define ESC_PV_ABSENT 1   /* the id is not a live pod of the context                       */
+#define ESC_PV_CLASS  2   /* the pod's class (or a C slot's room) is not the one it lies in */
+#define ESC_PV_VALUE  4   /* a stored word differs                                          */
+#define ESC_PV_BIND   8   /* pod_node[i] differs from the placement's binding (or'ed)       */
+typedef struct esc_pods_verify_report {
+    int64_t n_checked, n_absent, n_class, n_value, n_bind;
+    int64_t first_bad;    /* lowest batch index with a non-zero status, -1 if none */
+} esc_pods_verify_report;
+int32_t esc_pods_verify(esc_ctx* ctx, const int64_t* ids, const esc_pod_soa* pods,
+                        const uint32_t* pod_node /* NULL: bindings not compared */,
+                        uint8_t* status_out /* [n_pods] or NULL */, esc_pods_verify_report* out);
+int32_t esc_pods_live_ids(const esc_ctx* ctx, int64_t* ids_out, int64_t cap, int64_t* n_out);
 
 /* ----------------------------------------------------------------- ordering
  * K5: per-group creation-time order of the context's node shard (a18/a19):
