@@ -218,6 +218,7 @@ struct esc_ctx {
     bool ng_pending = false;
     bool force_wide = false;
     int k1_variant = 0;                                       // ESC_K1_VARIANT (measurement knob)
+    int k1_threads = 0;                                       // ESC_K1_THREADS (measurement knob); 0: 512
     // K pods of a class are laid out in order of pair0 / pod_sort (0: input order), so that a
     // K1 workgroup's share touches few pod-slot columns; ESC_POD_SORT
     uint32_t pod_sort = esc::FC_COL; // one K3 column per bucket (exact pair order serialises K1's LDS atomics: 0.65 ms)

@@ -135,12 +135,14 @@ enum WidePod : int { WP_CPU_LO = 0, WP_CPU_HI, WP_MEM_LO, WP_MEM_HI, WP_CNT, WP_
 // Per dry-mode group: the tracked members' count and split sums (K2 adds, K3 resets).
 enum TrkAcc : int { TA_CNT = 0, TA_CPU_LO, TA_CPU_HI, TA_MEM_LO, TA_MEM_HI, TA_K };
 
-// variant: 0 = the product K1 (512 threads: 8 waves per CU with up to 256 VGPRs, 3-4 K
-// tiles in flight per wave, one static share per workgroup); 7 = the product kernel without
-// the plan (PodDev::seg null: the weight-range walk and the full-row flush, exact); 3, 4,
-// 9-13 = timing ablations (3, 4 exact; 9-13 wrong results), present in the measurement
+// variant: 0 = the product K1 (one static share per workgroup); 7 = the product kernel without
+// the plan (PodDev::seg null: the weight-range walk and the full-row flush, exact); 3-6,
+// 9-13 = timing ablations (3-6 exact; 9-13 wrong results), present in the measurement
 // library only.  The variant is chosen by ESC_K1_VARIANT, which only the measurement
 // library reads (scripts/k1_variants.py).
+// threads: the workgroup's width.  512 is the product's (8 waves with up to 256 VGPRs, up to 3
+// K tiles in flight per wave); 1024 (16 waves with 128 VGPRs; the same share, LDS and results)
+// exists in the measurement library only (ESC_K1_THREADS), anything else is refused.
 struct DecCompact;
 // K1 diagnostics.  trace: per workgroup 8 words (esc_k1_trace; the share calibration reads words
 // 0-1): s_memrealtime (100 MHz) at start, after the K tiles, after the C tiles, after the
@@ -189,7 +191,7 @@ struct GroupList {
     int32_t first;
 };
 hipError_t launch_pod_reduce(const PodDev& p, const GroupDev& g, int32_t g0, int32_t gw, int nblk, int variant,
-                             uint64_t* part, int64_t* wide, const K1Diag& diag, hipStream_t st);
+                             int threads, uint64_t* part, int64_t* wide, const K1Diag& diag, hipStream_t st);
 hipError_t launch_pod_bigtiles(const PodDev& p, const GroupDev& g, const uint32_t* tiles, int64_t n_big,
                                int64_t* wide, hipStream_t st);
 // Compact decision record (32 B) that K3 / K4 write to pinned host memory each decision

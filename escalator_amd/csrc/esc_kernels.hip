@@ -38,11 +38,20 @@
 #ifndef ESC_PART
 #define ESC_PART 0
 #endif
+#ifndef ESC_MEASURE
+#define ESC_MEASURE 0   // 1: the measurement library (Makefile ABLATIONS=1)
+#endif
 #ifndef K1_PK_DS
-#define K1_PK_DS 6      // packed K tiles in flight per K1 wave (at most; the VGPR budget may allow fewer)
+#define K1_PK_DS 3      // packed K tiles in flight per K1 wave (at most; the VGPR budget may allow fewer)
 #endif
 #ifndef K1_PK8_DS
-#define K1_PK8_DS 8     // packed small K tiles in flight per K1 wave (at most)
+#define K1_PK8_DS 3     // packed small K tiles in flight per K1 wave (at most; 8 measured slower)
+#endif
+#ifndef K1_PK8_DS16
+#define K1_PK8_DS16 6   // the same in the 16-wave K1 (128 VGPRs a wave)
+#endif
+#ifndef K1_VG16
+#define K1_VG16 84      // VGPRs of a 16-wave K1 wave that hold tiles in flight
 #endif
 
 namespace esc {
@@ -492,12 +501,18 @@ __device__ __forceinline__ void k_run(const PodDev& P, const GroupDev& G, const 
     auto off = [&](int64_t u) { return u < b ? (uint32_t)((u - a) * BW * 4) : RUN_OOB; };
     // slots that fit the VGPR budget: 16 waves per CU leave 128 VGPRs a wave, 8 leave 256
     // (a packed tile is smaller, so more of them are in flight: up to K1_PK_DS)
-    constexpr int DSM = PK == 2 ? K1_PK8_DS : (PK ? K1_PK_DS : 4);
+    // (ABLATE bit 9: the earlier 8 / 6, for the A/B of DESIGN.md §8s)
+    constexpr int DSM = PK == 2 ? ((ABLATE & 512) ? 8 : K1_PK8_DS) : (PK ? ((ABLATE & 512) ? 6 : K1_PK_DS) : 4);
     constexpr int VG = PK == 2 ? 2 * L : 4 * L;
-    constexpr int DS0 = NW >= 16 ? (L <= 7 ? 3 : (L <= 10 ? 2 : 1))
+    // 16 waves: K1_VG16 of the 128 VGPRs go to tile slots (the rest: addresses, the pod being
+    // added, the flush descriptors), which is 3 packed tiles, 1 plain tile of the heaviest
+    // shape, and up to K1_PK8_DS16 packed small tiles (8 to 14 VGPRs each)
+    constexpr int DSM16 = PK == 2 ? K1_PK8_DS16 : 3;
+    constexpr int DS0 = NW >= 16 ? (K1_VG16 / VG >= DSM16 ? DSM16 : (K1_VG16 / VG >= 1 ? K1_VG16 / VG : 1))
                                  : (176 / VG >= DSM ? DSM : (176 / VG >= 1 ? 176 / VG : 1));
-    // timing knobs (ABLATE bits 6/7): cap the slots in flight at 2 / 3
-    constexpr int DS = (ABLATE & 64) ? (DS0 < 2 ? DS0 : 2) : ((ABLATE & 128) ? (DS0 < 3 ? DS0 : 3) : DS0);
+    // timing knobs (ABLATE bits 6/7/8): cap the slots in flight at 2 / 3 / 4
+    constexpr int DSC = (ABLATE & 64) ? 2 : ((ABLATE & 128) ? 3 : ((ABLATE & 256) ? 4 : DS0));
+    constexpr int DS = DS0 < DSC ? DS0 : DSC;
     KTile<R, NXP, PK> T[DS];
 #pragma unroll
     for (int d = 0; d < DS; ++d) {
@@ -1129,36 +1144,51 @@ __global__ __launch_bounds__(THREADS) void k_pod_reduce(PodDev P, GroupDev G, in
 #define ESC_K1(T, A, DC)                                                                                \
     hipLaunchKernelGGL((k_pod_reduce<T, A, DC>), dim3(nblk), dim3(T), k1_lds_bytes((uint32_t)gw), st, p, g, g0, \
                        (uint32_t)gw, part, wide, diag)
-#define ESC_K1_ARGS const PodDev &p, const GroupDev &g, int32_t g0, int32_t gw, int nblk, int variant, uint64_t *part, \
-                    int64_t *wide, const K1Diag &diag, hipStream_t st
+// at the width the runtime asks for: 512 threads, the product's; 1024 (16 waves per CU) is
+// instantiated in the measurement library only (ESC_K1_THREADS; slower)
+#if ESC_MEASURE
+#define ESC_K1W(A, DC)                         \
+    do {                                       \
+        if (threads == 1024) ESC_K1(1024, A, DC); \
+        else ESC_K1(512, A, DC);               \
+    } while (0)
+#else
+#define ESC_K1W(A, DC) ESC_K1(512, A, DC)
+#endif
+#define ESC_K1_ARGS const PodDev &p, const GroupDev &g, int32_t g0, int32_t gw, int nblk, int variant, int threads, \
+                    uint64_t *part, int64_t *wide, const K1Diag &diag, hipStream_t st
 hipError_t launch_pod_reduce_ablation(ESC_K1_ARGS) __attribute__((weak));
 
 #if ESC_PART == 0
 hipError_t launch_pod_reduce(ESC_K1_ARGS) {
+    if (threads != 512 && !(ESC_MEASURE && threads == 1024)) return hipErrorInvalidValue;
     switch (variant) {
-        case 0: case 7: ESC_K1(512, 0, 3); break;   // 7: the runtime passes no plan (pod_dev)
+        case 0: case 7: ESC_K1W(0, 3); break;     // 7: the runtime passes no plan (pod_dev)
         default:                                  // timing-only ablations (measurement library only)
             if (!launch_pod_reduce_ablation) return hipErrorInvalidValue;
-            return launch_pod_reduce_ablation(p, g, g0, gw, nblk, variant, part, wide, diag, st);
+            return launch_pod_reduce_ablation(p, g, g0, gw, nblk, variant, threads, part, wide, diag, st);
     }
     return hipGetLastError();
 }
 #elif ESC_PART == 2
 hipError_t launch_pod_reduce_ablation(ESC_K1_ARGS) {
     switch (variant) {
-        case 3: ESC_K1(512, 64, 3); break;       // <= 2 K tiles in flight per wave
-        case 4: ESC_K1(512, 128, 3); break;      // <= 3 K tiles in flight per wave
+        case 3: ESC_K1W(64, 3); break;           // <= 2 K tiles in flight per wave
+        case 4: ESC_K1W(128, 3); break;          // <= 3 K tiles in flight per wave
+        case 5: ESC_K1W(256, 3); break;          // <= 4 K tiles in flight per wave
+        case 6: ESC_K1W(512, 3); break;          // up to 8 packed small / 6 packed tiles in flight (the 8-wave kernel's before §8s)
         // Timing-only ablations (wrong results; scripts/k1_variants.py), see k_pod_reduce.
-        case 9: ESC_K1(512, 1, 3); break;        // LDS atomics replaced by a sink
-        case 10: ESC_K1(512, 2, 3); break;       // C tiles only
-        case 11: ESC_K1(512, 4, 3); break;       // K tiles only
-        case 12: ESC_K1(512, 4 | 32, 3); break;  // K tiles, loads only
-        case 13: ESC_K1(512, 2 | 32, 3); break;  // C tiles, loads only
+        case 9: ESC_K1W(1, 3); break;            // LDS atomics replaced by a sink
+        case 10: ESC_K1W(2, 3); break;           // C tiles only
+        case 11: ESC_K1W(4, 3); break;           // K tiles only
+        case 12: ESC_K1W(4 | 32, 3); break;      // K tiles, loads only
+        case 13: ESC_K1W(2 | 32, 3); break;      // C tiles, loads only
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 #endif
+#undef ESC_K1W
 #undef ESC_K1
 #undef ESC_K1_ARGS
 

@@ -989,9 +989,13 @@ int32_t stage_mark(esc_ctx* c) {
 int32_t launch_k1(esc_ctx* c, int r, const GroupDev& g, uint64_t* trace, hipStream_t st) {
     const PodDev p = pod_dev(c, r);
     const int32_t S = (int32_t)pod_slots(c);
-    for (int32_t g0 = 0; g0 < S; g0 += POD_WINDOW_MAX)
-        HIP_TRY(launch_pod_reduce(p, g, g0, std::min(POD_WINDOW_MAX, S - g0), c->nblk, c->k1_variant, c->d_pod_part,
-                                  c->d_wide_pod, K1Diag{trace}, st));
+    for (int32_t g0 = 0; g0 < S; g0 += POD_WINDOW_MAX) {
+        const int32_t gw = std::min(POD_WINDOW_MAX, S - g0);
+        // 512 threads at every window: 1024 (4 waves per SIMD where a full window leaves a CU one
+        // workgroup) measured slower and exists in the measurement library only
+        HIP_TRY(launch_pod_reduce(p, g, g0, gw, c->nblk, c->k1_variant, c->k1_threads ? c->k1_threads : 512,
+                                  c->d_pod_part, c->d_wide_pod, K1Diag{trace}, st));
+    }
     HIP_TRY(launch_pod_bigtiles(p, g, c->pods[r].big, c->n_big, c->d_wide_pod, st));
     return ESC_OK;
 }
@@ -1178,6 +1182,7 @@ int32_t esc_ctx_create(const esc_group_spec* groups, int32_t n_groups, int32_t d
     // measurement knobs: read by the measurement library only (Makefile ABLATIONS=1,
     // libescalator_hip_measure.so); the product library's results depend on its inputs alone
     if (const char* v = std::getenv("ESC_K1_VARIANT")) c->k1_variant = std::atoi(v);
+    if (const char* v = std::getenv("ESC_K1_THREADS")) c->k1_threads = std::atoi(v);   // 512 / 1024
     if (const char* v = std::getenv("ESC_POD_SORT")) c->pod_sort = (uint32_t)std::max(0, std::atoi(v));
     if (const char* v = std::getenv("ESC_K1_FULL_FLUSH")) c->full_flush = std::atoi(v) != 0;
     if (const char* v = std::getenv("ESC_K3_ABLATE")) c->k3_ablate = std::atoi(v);
