@@ -108,6 +108,14 @@ class PodsVerifyReport(C.Structure):
     _fields_ = [(n, i64) for n in PODS_VERIFY_FIELDS]
 
 
+NV_ABSENT, NV_SHAPE, NV_STATUS, NV_FACTS, NV_INST = 1, 2, 4, 8, 16   # ESC_NV_*: a node's status byte from esc_nodes_verify
+NODES_VERIFY_FIELDS = ["n_checked", "n_absent", "n_shape", "n_status", "n_facts", "n_inst", "first_bad"]
+
+
+class NodesVerifyReport(C.Structure):
+    _fields_ = [(n, i64) for n in NODES_VERIFY_FIELDS + ["reserved"]]
+
+
 PODS_COMPACT_FIELDS = ["rehomed", "classes_created", "k_tiles_before", "k_tiles_after", "k1_bytes_before",
                        "k1_bytes_after", "moved", "c_free_before", "c_free_after"]
 
@@ -240,6 +248,8 @@ _SIGS = {
     "esc_audit_pods": (i32, [VP, u32, P(PodAuditReport)]),
     "esc_pods_verify": (i32, [VP, P(i64), P(PodSoA), P(u32), P(C.c_uint8), P(PodsVerifyReport)]),
     "esc_pods_live_ids": (i32, [VP, P(i64), i64, P(i64)]),
+    "esc_nodes_verify": (i32, [VP, P(i64), P(NodeSoA), P(i64), P(C.c_uint8), P(i64), P(C.c_uint8), P(NodesVerifyReport)]),
+    "esc_nodes_live_ids": (i32, [VP, P(i64), i64, P(i64)]),
     "esc_set_metrics": (i32, [VP, i32]),
     "esc_metrics_results": (i32, [VP, P(GroupMetrics)]),
     "esc_use_graph": (i32, [VP, i32]),

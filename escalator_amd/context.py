@@ -742,6 +742,46 @@ class Context:
                     "esc_pods_live_ids")
         return out[:n.value]
 
+    def nodes_verify(self, ids, nodes: dict, taint_s=None, no_delete=None, inst_ns=None) -> tuple[np.ndarray, dict]:
+        """esc_nodes_verify: a read-only compare of packed nodes (a ``pack`` result, as
+        ``nodes_relabel`` takes them) with the resident node table.  ``taint_s`` / ``no_delete``
+        (``nodes_facts``' values) and ``inst_ns`` (``nodes_instantiated``'s) are compared when
+        given.  Returns ``(status, report)``: one uint8 per node (0 = it matches; bits
+        ``_lib.NV_ABSENT``, ``NV_SHAPE``, ``NV_STATUS``, ``NV_FACTS``, ``NV_INST``, each naming the
+        call that repairs it) and the report's ``n_checked``, a count per bit and ``first_bad``
+        (the lowest batch index with a status, -1)."""
+        ids = np.ascontiguousarray(ids, np.int64)
+        ns, keep = node_soa(nodes)
+        if len(ids) != ns.n_nodes:
+            raise ValueError("nodes_verify: one id per node")
+        status = np.zeros(len(ids), np.uint8)
+
+        def opt(a, dt, ct):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dt)
+            if len(a) != len(ids):
+                raise ValueError("nodes_verify: a fact array must have one entry per node")
+            return a, a.ctypes.data_as(C.POINTER(ct))
+        t, tp = opt(taint_s, np.int64, C.c_int64)
+        d, dp = opt(no_delete, np.uint8, C.c_uint8)
+        s, sp = opt(inst_ns, np.int64, C.c_int64)
+        rep = L.NodesVerifyReport()
+        L.check(self.lib.esc_nodes_verify(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ns), tp, dp, sp,
+                                          status.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rep)), "esc_nodes_verify")
+        del keep, t, d, s
+        return status, {n: int(getattr(rep, n)) for n in L.NODES_VERIFY_FIELDS}
+
+    def nodes_live_ids(self) -> np.ndarray:
+        """esc_nodes_live_ids (host only): the live node-table slots, ascending."""
+        n = C.c_int64()
+        L.check(self.lib.esc_nodes_live_ids(self.handle, None, 0, C.byref(n)), "esc_nodes_live_ids")
+        out = np.zeros(n.value, np.int64)
+        if n.value:
+            L.check(self.lib.esc_nodes_live_ids(self.handle, out.ctypes.data_as(C.POINTER(C.c_int64)), n.value, C.byref(n)),
+                    "esc_nodes_live_ids")
+        return out[:n.value]
+
     # ------------------------------------------------------------- ordering
     def sort_nodes(self):
         L.check(self.lib.esc_sort_nodes(self.handle), "esc_sort_nodes")

@@ -491,18 +491,27 @@ class ResidentController(Controller):
     ``resync_every=k`` (keyword-only, off by default, ``None``): every k-th scan's flush is
     ``events.resync(ctx)`` — the flush, then every pod of the object store compared with the
     device (``ctx.pods_verify``) and what differs repaired through the event calls — before the
-    audits and the decision; ``resyncs`` counts the passes, ``last_resync`` is the last result."""
+    audits and the decision; ``resyncs`` counts the passes, ``last_resync`` is the last result.
+
+    ``node_resync_every=k`` (keyword-only, off by default, ``None``): every k-th scan runs
+    ``events.resync_nodes(ctx)`` after the flush (or the pod resync) and before the audits and the
+    decision — every node of the object store compared with the resident node table
+    (``ctx.nodes_verify``) and what differs repaired through the node event calls;
+    ``node_resyncs`` counts the passes, ``last_node_resync`` is the last result."""
 
     REBUILT_CHECKS = ("ENTRY", "FIRST", "REGION", "OCC", "TRACKER")
     # the pod audit is off unless the constructor's keyword turns it on
     pod_audit_every, pod_audits, pod_audit_failures, last_pod_audit = 0, 0, 0, None
     # and so is the resync of the pods' values
     resync_every, resyncs, last_resync = None, 0, None
+    # and of the nodes'
+    node_resync_every, node_resyncs, last_node_resync = None, 0, None
 
     def __init__(self, groups: list[dict], device: int = 0, dry_mode: bool = False, clock=None, actuator=None,
                  selection_slack: int = 4, spare: float = 0.5, audit_every: int = 0, node_rebuild: bool = False,
                  node_compact: bool = False, pod_grow: bool = False, *, pod_compact: float | None = None,
-                 pod_audit_every: int = 0, resync_every: int | None = None):
+                 pod_audit_every: int = 0, resync_every: int | None = None,
+                 node_resync_every: int | None = None):
         super().__init__(groups, device=device, dry_mode=dry_mode, clock=clock, actuator=actuator,
                          selection_slack=selection_slack)
         from .events import EventQueue
@@ -530,6 +539,10 @@ class ResidentController(Controller):
         self.resync_every = int(resync_every) if resync_every else None
         self.resyncs = 0
         self.last_resync = None
+        # the nodes' values: every node_resync_every-th scan runs events.resync_nodes; None = never
+        self.node_resync_every = int(node_resync_every) if node_resync_every else None
+        self.node_resyncs = 0
+        self.last_node_resync = None
 
     def _learned(self, name: str, j: int, t: int):
         """The queue keeps the cache: it drops a name on node_delete and re-sends the cache
@@ -581,6 +594,11 @@ class ResidentController(Controller):
         else:
             self.events.flush(self.ctx)
         self.scans += 1
+        if self.node_resync_every and self.scans % self.node_resync_every == 0:
+            touched = self.events.touched_nodes                 # (its own flush resets the flag)
+            self.last_node_resync = self.events.resync_nodes(self.ctx)
+            self.events.touched_nodes = self.events.touched_nodes or touched
+            self.node_resyncs += 1
         if self.audit_every and self.scans % self.audit_every == 0:
             self._audit()
         if self.pod_audit_every and self.scans % self.pod_audit_every == 0:

@@ -8,6 +8,8 @@
 //   esc_pod_audit.hip  the pod side's read-only audit (esc_audit_pods)
 //   esc_pod_verify.hip  the resident pods compared with a caller's batch (esc_pods_verify,
 //                     esc_pods_live_ids) and its kernel
+//   esc_node_verify.hip  the resident nodes compared with a caller's batch (esc_nodes_verify,
+//                     esc_nodes_live_ids) and its kernel; the compare rule is esc_node_verify.h
 // Everything else (esc_multi.hip, esc_list.hip, the packer, the generator) sees esc_ctx as
 // opaque.  Helpers that cross a file are declared at the end, each defined in the file of its
 // subsystem; the small ones are inline here.

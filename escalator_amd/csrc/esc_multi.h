@@ -78,6 +78,9 @@ int32_t multi_audit_pods(esc_ctx* c, uint32_t checks, esc_pod_audit_report* out)
 int32_t multi_pods_verify(esc_ctx* c, const int64_t* ids, const esc_pod_soa* p, const uint32_t* pod_node, uint8_t* status_out,
                           esc_pods_verify_report* out);                           // routed by id, merged in batch order
 int32_t multi_pods_live_ids(const esc_ctx* c, int64_t* ids_out, int64_t cap, int64_t* n_out);
+int32_t multi_nodes_verify(esc_ctx* c, const int64_t* ids, const esc_node_soa* s, const int64_t* taint_s, const uint8_t* no_delete,
+                           const int64_t* inst_ns, uint8_t* status_out,
+                           esc_nodes_verify_report* out);                          // every device's copy, statuses or-ed
 int32_t multi_nodes_add(esc_ctx* c, const esc_node_soa* s, int64_t* ids_out);
 int32_t multi_nodes_delete(esc_ctx* c, const int64_t* ids, int64_t n);
 int32_t multi_nodes_rebuild(esc_ctx* c);                                          // every device's node side (esc_nodes_rebuild)

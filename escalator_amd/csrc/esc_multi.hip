@@ -640,6 +640,34 @@ int32_t multi_pods_live_ids(const esc_ctx* c, int64_t* ids_out, int64_t cap, int
     return total > cap && !(cap == 0 && !ids_out) ? ESC_E_LIMIT : ESC_OK;
 }
 
+// esc_nodes_verify: every device holds the whole node table and verifies its own copy.  A node's
+// status is the OR over the devices (a difference on one device alone is found) and the report
+// is counted from the or-ed bytes, so a node that differs on two devices counts once.
+int32_t multi_nodes_verify(esc_ctx* c, const int64_t* ids, const esc_node_soa* s, const int64_t* taint_s, const uint8_t* no_delete,
+                           const int64_t* inst_ns, uint8_t* status_out, esc_nodes_verify_report* out) {
+    if (!out || !s) return ESC_E_INVAL;
+    if (M(c).diverged) return ESC_E_STATE;
+    const int64_t n = std::max<int64_t>(s->n_nodes, 0);
+    std::vector<uint8_t> all((size_t)std::max<int64_t>(n, 1), 0), stat(all.size(), 0);
+    esc_nodes_verify_report r = {0, 0, 0, 0, 0, 0, -1, 0};
+    for (int i = 0; i < nsub(c); ++i) {
+        if (int32_t rc = esc_nodes_verify(M(c).subs[i], ids, s, taint_s, no_delete, inst_ns, stat.data(), &r)) return rc;
+        for (int64_t j = 0; j < n; ++j) all[(size_t)j] |= stat[(size_t)j];
+    }
+    esc_nodes_verify_report sum = {r.n_checked, 0, 0, 0, 0, 0, -1, 0};
+    for (int64_t j = 0; j < n; ++j) {
+        const uint8_t b = all[(size_t)j];
+        if (!b) continue;
+        if (sum.first_bad < 0) sum.first_bad = j;
+        sum.n_absent += (b & ESC_NV_ABSENT) != 0; sum.n_shape += (b & ESC_NV_SHAPE) != 0;
+        sum.n_status += (b & ESC_NV_STATUS) != 0; sum.n_facts += (b & ESC_NV_FACTS) != 0;
+        sum.n_inst += (b & ESC_NV_INST) != 0;
+    }
+    if (status_out && n) std::memcpy(status_out, all.data(), (size_t)n);
+    *out = sum;
+    return ESC_OK;
+}
+
 int32_t multi_nodes_relabel(esc_ctx* c, const int64_t* ids, const esc_node_soa* s) {
     if (M(c).diverged) return ESC_E_STATE;
     if (int32_t rc = nodes_relabel_check(M(c).subs[0], ids, s)) return rc;   // nothing applied anywhere

@@ -18,7 +18,9 @@ flush that applied cleanly is followed by one ``pods_compact`` (the pod side re-
 classes shrunk to the load's rule, parked pods back in their classes, every id kept) when
 ``pods_slack`` reports ``(k_tiles - k_tiles_rule) * 256 + parked >= frac * live pods``.
 ``resync(ctx)`` is the informers' periodic resync: the whole object store compared with the device
-(``pods_verify``) and only what differs repaired through the calls above.
+(``pods_verify``) and only what differs repaired through the calls above; ``resync_nodes(ctx)`` is
+the same for the nodes (``nodes_verify``: labels, creation time, cordon, taint, allocatable, taint
+time, no-delete flag, instantiation time).
 
 It holds the current objects (plain-dict records, escalator_amd/objects.py) — the truth a
 reload is built from — and, beside them, what the device last saw of each.  Ingest
@@ -98,6 +100,8 @@ class EventQueue:
         self.pod_compact_failures = 0
         self.resyncs = 0                           # resync() calls, and the pods each kind of repair took
         self.resync_repairs = {"absent": 0, "class": 0, "value": 0, "bind": 0, "orphans": 0}
+        self.node_resyncs = 0                      # resync_nodes() calls, and the nodes each kind of repair took
+        self.node_resync_repairs = {"absent": 0, "shape": 0, "status": 0, "facts": 0, "inst": 0, "orphans": 0}
         self.pods: dict[str, dict] = {}            # the object store: key -> pod, name -> node
         self.nodes: dict[str, dict] = {}           # (insertion order = arrival order)
         self._dev_pods: dict[str, dict] = {}       # the records the device holds, as last flushed
@@ -473,6 +477,103 @@ class EventQueue:
         for k in [k for k, i in pid.items() if i in gone and k not in self.pods]:
             heapq.heappush(self._free, pid.pop(k))
             self._dev_pods.pop(k, None)
+        return out
+
+    def resync_nodes(self, ctx, chunk: int = 65536) -> dict:
+        """The node half of the informers' resync: after a flush, every node of the object store
+        that has an index is packed as a flush packs it and compared with the resident node table
+        (``nodes_verify``, `chunk` nodes per call) together with its facts (taint time, no-delete)
+        and the instantiation time the queue holds for it (unknown otherwise); the device's live
+        slots are compared with the identity map.  What differs is repaired through the flush's
+        own calls in the flush's order, an ESC_E_LIMIT answered as a flush answers it
+        (``nodes_rebuild`` / ``nodes_compact`` when enabled, else one reload): the slots no node of
+        the map has in one ``nodes_delete``; the nodes reported absent lose their index and are
+        added again (``nodes_add``, their pods bound again); the nodes of another shape in one
+        ``nodes_relabel`` (which rewrites the status too); the others of another status in one
+        ``nodes_update``; other facts in one ``nodes_facts``; other instantiation times in one
+        ``nodes_instantiated``.  Returns ``{checked, absent, shape, status, facts, inst, orphans,
+        reloaded}``."""
+        from ._lib import NV_ABSENT, NV_FACTS, NV_INST, NV_SHAPE, NV_STATUS
+        self.flush(ctx)
+        self.node_resyncs += 1
+        idx = self._node_idx
+        unknown = -(1 << 63)
+        bits = (("absent", NV_ABSENT), ("shape", NV_SHAPE), ("status", NV_STATUS), ("facts", NV_FACTS), ("inst", NV_INST))
+        out = {"checked": 0, "absent": 0, "shape": 0, "status": 0, "facts": 0, "inst": 0, "orphans": 0, "reloaded": False}
+        names = [m for m in self.nodes if m in idx]
+        found = {name: [] for name, _ in bits}
+        for a in range(0, len(names), max(1, int(chunk))):
+            ms = names[a:a + max(1, int(chunk))]
+            _, packed = ctx.pack([], [self.nodes[m] for m in ms])
+            f = [_facts(self.nodes[m]) for m in ms]
+            status, _rep = ctx.nodes_verify(np.array([idx[m] for m in ms], np.int64), packed,
+                                            np.array([t for t, _ in f], np.int64), np.array([d for _, d in f], np.uint8),
+                                            np.array([self.inst_ns.get(m, unknown) for m in ms], np.int64))
+            status = np.asarray(status, np.uint8)
+            out["checked"] += len(ms)
+            for name, bit in bits:
+                found[name] += [ms[i] for i in np.flatnonzero(status & bit)]
+        # the other direction: live slots the identity map does not name (their delete never arrived)
+        orphans = [int(j) for j in ctx.nodes_live_ids() if int(j) not in self._idx_node]
+        out["orphans"] = len(orphans)
+        log = logging.getLogger(__name__)
+        for name in ("absent", "shape", "status", "facts", "inst", "orphans"):
+            if name != "orphans":
+                out[name] = len(found[name])
+            if out[name]:
+                self.node_resync_repairs[name] += out[name]
+                log.warning("resync: %d nodes %s", out[name],
+                            {"absent": "missing on the device", "shape": "with other labels or creation time on the device",
+                             "status": "with another cordon, taint or allocatable on the device",
+                             "facts": "with another taint time or no-delete flag on the device",
+                             "inst": "with another instantiation time on the device",
+                             "orphans": "on the device and not in the store"}[name])
+        absent = found["absent"]
+        shaped = set(found["shape"])
+        relabel = found["shape"]
+        update = [m for m in found["status"] if m not in shaped]
+        facts = absent + found["facts"]
+        inst = [m for m in absent if m in self.inst_ns] + found["inst"]
+        try:
+            if orphans:
+                self._call("nodes_delete", len(orphans), ctx.nodes_delete, np.array(orphans, np.int64))
+            if absent:
+                for m in absent:                               # the index names no node: the node is new again
+                    self._idx_node.pop(idx.pop(m), None)
+                    self._dev_nodes.pop(m, None)
+                _, packed = ctx.pack([], [self.nodes[m] for m in absent])
+                ids = self._node_call(ctx, "nodes_add", len(absent), len(absent), len(packed.get("xl_pair", ())),
+                                      ctx.nodes_add, packed)
+                for m, j in zip(absent, ids):
+                    idx[m] = int(j)
+                    self._idx_node[int(j)] = m
+                self.touched_nodes = True
+            if relabel:
+                _, packed = ctx.pack([], [self.nodes[m] for m in relabel])
+                self._node_call(ctx, "nodes_relabel", len(relabel), 0, 0, ctx.nodes_relabel,
+                                np.array([idx[m] for m in relabel], np.int64), packed)
+            if update:
+                _, packed = ctx.pack([], [self.nodes[m] for m in update])
+                self._call("nodes_update", len(update), ctx.nodes_update, np.array([idx[m] for m in update], np.int64),
+                           packed["flags"], packed["cpu"], packed["mem"])
+            if facts:
+                f = [_facts(self.nodes[m]) for m in facts]
+                self._call("nodes_facts", len(facts), ctx.nodes_facts, np.array([idx[m] for m in facts], np.int64),
+                           np.array([t for t, _ in f], np.int64), np.array([d for _, d in f], np.uint8))
+            if inst:
+                ctx.nodes_instantiated(np.array([idx[m] for m in inst], np.int64),
+                                       np.array([self.inst_ns.get(m, unknown) for m in inst], np.int64))
+            # the pods that name a node added again, as for a node that arrives after its pods
+            pid = self._pod_id
+            bind = [k for m in absent for k in sorted(self._by_node.get(m, ()), key=lambda k: pid.get(k, -1)) if k in pid]
+            self._bind_pods(ctx, bind)
+        except _Reload as e:
+            self.reload_causes.append("resync_nodes:%s" % e)
+            self._reload(ctx, {}, {})
+            out["reloaded"] = True
+            return out
+        for m in absent + relabel + update + facts:
+            self._dev_nodes[m] = self.nodes[m]
         return out
 
     def _reload(self, ctx, dirty_p, dirty_n):

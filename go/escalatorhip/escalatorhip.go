@@ -1156,3 +1156,82 @@ func (x *Context) PodsLiveIDs() ([]int64, error) {
 	}
 	return ids[:int(n)], nil
 }
+
+// A node's status byte from NodesVerify (ESC_NV_*): 0 = the device holds the node as offered.
+// Every bit names the call that repairs it.
+const (
+	NodeAbsent uint8 = C.ESC_NV_ABSENT // the id names no live node of the context: NodesAdd
+	NodeShape  uint8 = C.ESC_NV_SHAPE  // a label pair, the label count or the creation time differs: NodesRelabel
+	NodeStatus uint8 = C.ESC_NV_STATUS // the cordon, the taint's presence or allocatable differs: NodesUpdate
+	NodeFacts  uint8 = C.ESC_NV_FACTS  // the taint time or the no-delete flag differs: esc_nodes_facts
+	NodeInst   uint8 = C.ESC_NV_INST   // the instantiation time differs: SetInstantiated
+)
+
+// NodesVerifyReport is esc_nodes_verify's report; FirstBad is the lowest batch index with a
+// non-zero status, -1 if none.
+type NodesVerifyReport struct {
+	Checked, Absent, Shape, Status, Facts, Inst, FirstBad int64
+}
+
+// NodesVerify compares nodes, as the informer's store holds them, with the resident node table
+// (the node half of the informers' resync): read-only, one status byte per node.  taintS (Unix
+// seconds, math.MinInt64 = no taint time), noDelete (non-zero = safe from deletion) and instNs
+// (Unix ns, math.MinInt64 = unknown) are compared when not nil.  Mismatches are data, not an
+// error: NodeShape nodes go through NodesRelabel (which rewrites the status too), the other
+// NodeStatus nodes through NodesUpdate, NodeInst nodes through SetInstantiated; a NodeAbsent node
+// is added again.
+func (x *Context) NodesVerify(ids []int64, nodes []*v1.Node, taintS []int64, noDelete []uint8, instNs []int64) ([]uint8, *NodesVerifyReport, error) {
+	n := len(ids)
+	if n != len(nodes) || (taintS != nil && len(taintS) != n) || (noDelete != nil && len(noDelete) != n) ||
+		(instNs != nil && len(instNs) != n) {
+		return nil, nil, fmt.Errorf("escalatorhip: %d ids, %d nodes, %d taint times, %d no-delete flags, %d instantiation times",
+			n, len(nodes), len(taintS), len(noDelete), len(instNs))
+	}
+	status := make([]uint8, n)
+	out := &NodesVerifyReport{FirstBad: -1}
+	if n == 0 {
+		return status, out, nil
+	}
+	err := x.pack(nil, nodes, nil, false, func(_ *C.esc_pod_soa, ns *C.esc_node_soa) error {
+		var rep C.esc_nodes_verify_report
+		var ts, in *C.int64_t
+		var nd *C.uint8_t
+		if taintS != nil {
+			ts = (*C.int64_t)(unsafe.Pointer(ptr(taintS)))
+		}
+		if noDelete != nil {
+			nd = (*C.uint8_t)(unsafe.Pointer(ptr(noDelete)))
+		}
+		if instNs != nil {
+			in = (*C.int64_t)(unsafe.Pointer(ptr(instNs)))
+		}
+		rc := C.esc_nodes_verify(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), ns, ts, nd, in, (*C.uint8_t)(unsafe.Pointer(ptr(status))), &rep)
+		if rc != C.ESC_OK {
+			return rcErr("esc_nodes_verify", rc)
+		}
+		*out = NodesVerifyReport{Checked: int64(rep.n_checked), Absent: int64(rep.n_absent), Shape: int64(rep.n_shape),
+			Status: int64(rep.n_status), Facts: int64(rep.n_facts), Inst: int64(rep.n_inst), FirstBad: int64(rep.first_bad)}
+		return nil
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	return status, out, nil
+}
+
+// NodesLiveIDs returns the live node-table slots of the context, ascending (host only): the other
+// direction of a resync, the nodes the device holds and the store does not (NodesDelete them).
+func (x *Context) NodesLiveIDs() ([]int64, error) {
+	var n C.int64_t
+	if rc := C.esc_nodes_live_ids(x.c, nil, 0, &n); rc != C.ESC_OK {
+		return nil, rcErr("esc_nodes_live_ids", rc)
+	}
+	ids := make([]int64, int(n))
+	if n == 0 {
+		return ids, nil
+	}
+	if rc := C.esc_nodes_live_ids(x.c, (*C.int64_t)(unsafe.Pointer(ptr(ids))), n, &n); rc != C.ESC_OK {
+		return nil, rcErr("esc_nodes_live_ids", rc)
+	}
+	return ids[:int(n)], nil
+}

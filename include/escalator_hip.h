@@ -1001,6 +1001,66 @@ int32_t esc_pods_verify(esc_ctx* ctx, const int64_t* ids, const esc_pod_soa* pod
                         const uint32_t* pod_node /* NULL: bindings not compared */,
                         uint8_t* status_out /* [n_pods] or NULL */, esc_pods_verify_report* out);
 int32_t esc_pods_live_ids(const esc_ctx* ctx, int64_t* ids_out, int64_t cap, int64_t* n_out);
+/* esc_nodes_verify is the node side's resync: a read-only compare of a batch of nodes, as the
+ * caller's store holds them, with the resident node table and its per-node facts.  ids and nodes
+ * are exactly what esc_nodes_relabel takes (n_trk = 0; a caller's ESC_NF_TRACKED is ignored, the
+ * tracker is the context's); the three fact arrays are esc_nodes_facts' and
+ * esc_nodes_instantiated's (INT64_MIN = no taint time / an unknown instantiation time, a non-zero
+ * no_delete = safe from deletion), each NULL when it is not to be compared.  Node i of the batch
+ * gets one status byte:
+ *   0              the node matches in everything compared
+ *   ESC_NV_ABSENT  the id names no live node of the context: an id at or above the table's
+ *                  capacity, a free spare slot, a deleted slot.  ABSENT ends the compare
+ *   ESC_NV_SHAPE   label0, the extra-label count, an extra label pair (word for word: both sides
+ *                  are ascending lists) or created_ns differs.  Repair: esc_nodes_relabel, which
+ *                  rewrites every field, so SHAPE | STATUS needs the relabel alone
+ *   ESC_NV_STATUS  ESC_NF_UNSCHED, ESC_NF_TAINTED, cpu or mem differs.  Repair: esc_nodes_update
+ *   ESC_NV_FACTS   the taint time or the no-delete flag (compared as != 0 on both sides) differs.
+ *                  Repair: esc_nodes_facts
+ *   ESC_NV_INST    the instantiation time differs.  Repair: esc_nodes_instantiated
+ * The four bits past ABSENT are independent and or-ed.  cpu, mem, created_ns and the two times are
+ * compared as exact int64 values; of the flags word only ESC_NF_UNSCHED, ESC_NF_TAINTED and the
+ * extra-label count are compared (ESC_NF_TRACKED belongs to the context on both sides).
+ * The report: n_checked = n_nodes, a count per status bit and first_bad, the lowest batch index
+ * with a non-zero status (-1: none); status_out ([n_nodes]) may be NULL.  Deterministic: counts are
+ * sums, first_bad a minimum.  Mismatches are data (ESC_OK); nothing is repaired.
+ * ESC_E_INVAL with nothing reported for a NULL out, a NULL array with n_nodes > 0, n_trk != 0, an
+ * id outside [0, 2^31), a repeated id, or extra-label counts past n_xl; ESC_E_NODEV without a
+ * device; ESC_E_STATE before esc_load_nodes, while the node side is stale, or with taint_unix_s or
+ * no_delete given and no placement loaded; n_nodes == 0 is ESC_OK with a zero report.
+ * Read-only, as esc_pods_verify is: it runs on the context's stream behind whatever is pending and
+ * writes only its own scratch; captured steps, the last decision's records, selections, reaping
+ * and new-node results, the age index, the K1 plan and its calibration stay.  No device word is an
+ * index: an id at or above the table's capacity (or the columns' recorded allocations) is ABSENT
+ * by the host and never read; a node's extra labels are read at the host mirror's offset, and
+ * only when that offset plus the batch's count lies inside the device's label words (else SHAPE
+ * by the host) and the device's count equals the batch's (else SHAPE, no label word read), in a
+ * loop bounded by the batch's count.  The batch goes up in chunks through esc_audit_pods' pinned
+ * staging buffer (one 64-B record per node and its label words), one launch per chunk, so the
+ * extra device memory (two 4 MiB chunk buffers and the report's words) does not grow with
+ * n_nodes.  Multi-device: every device verifies its own copy of the table; a node's status is the
+ * OR over the devices and the counts are those of the or-ed bytes; every rank of a sharded job
+ * holds the whole table and verifies its own copy (no collective).
+ * esc_nodes_live_ids (host only, no device needed): the live table slots, ascending, for the
+ * other direction of a resync (nodes the context holds and the store does not), with
+ * esc_pods_live_ids' contract: ids_out == NULL with cap == 0 sizes the answer (*n_out);
+ * ESC_E_LIMIT when cap is short (*n_out still set); ESC_E_STATE before esc_load_nodes. */
+#define ESC_NV_ABSENT 1   /* the id names no live node of the context */
+#define ESC_NV_SHAPE  2   /* label0, the extra-label count or an extra label pair, or created_ns differs: esc_nodes_relabel */
+#define ESC_NV_STATUS 4   /* ESC_NF_UNSCHED / ESC_NF_TAINTED, cpu or mem differs: esc_nodes_update */
+#define ESC_NV_FACTS  8   /* taint time or no-delete differs: esc_nodes_facts */
+#define ESC_NV_INST   16  /* instantiation time differs: esc_nodes_instantiated */
+typedef struct esc_nodes_verify_report {
+    int64_t n_checked, n_absent, n_shape, n_status, n_facts, n_inst;
+    int64_t first_bad;    /* lowest batch index with a non-zero status, -1 if none */
+    int64_t reserved;
+} esc_nodes_verify_report;   /* 64 bytes */
+int32_t esc_nodes_verify(esc_ctx* ctx, const int64_t* ids, const esc_node_soa* nodes,
+                         const int64_t* taint_unix_s /* NULL: not compared */,
+                         const uint8_t* no_delete    /* NULL: not compared */,
+                         const int64_t* inst_unix_ns /* NULL: not compared */,
+                         uint8_t* status_out /* [n_nodes] or NULL */, esc_nodes_verify_report* out);
+int32_t esc_nodes_live_ids(const esc_ctx* ctx, int64_t* ids_out, int64_t cap, int64_t* n_out);
 
 /* ----------------------------------------------------------------- ordering
  * K5: per-group creation-time order of the context's node shard (a18/a19):

@@ -11,7 +11,7 @@ FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math 
 $HIPCC $FL "$@" -DESC_PART=0 -c esc_kernels.hip -o $B/esc_kernels.o
 O=../../build/csrc
 # the host runtime's files (the Makefile's SRCS_RT)
-RT_SRCS="esc_runtime esc_rebuild"
+RT_SRCS="esc_runtime esc_rebuild esc_pod_grow esc_pod_compact esc_pod_audit esc_pod_verify esc_node_verify"
 RT_DIR=$O
 if [ -n "$REBUILD_RT" ]; then            # flags that change the runtime's view too (e.g. -DESC_ORD_CHUNK)
     for f in $RT_SRCS; do $HIPCC $FL "$@" -c $f.hip -o $B/$f.o; done
